@@ -6,7 +6,7 @@ A "step" is the reference's loop body (main.py:165-169): zero_grad -> forward ->
 (weak scaling: global batch = 32 * n_gpus, BASELINE.json configs[3] at 8 GPUs).  Inputs are resident in
 HBM before the timed region.  Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype f32|bf16]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype f32|bf16] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 --config (default c2 = the headline; the others are the remaining single-GPU entries of BASELINE.json `configs`):
@@ -239,6 +239,34 @@ def pmc_traffic(config, dtype):
     return {k: int(v["hbm_bytes"]) for k, v in rec.items()}, name
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the timed step hands its caller after the LAST timed step -- the loss, the updated parameters and the
+    gradients of that step (param.grad) -- as float32 DIR/<name>.npy.  An array too large for its share of the 64 MB budget is replaced
+    by a fixed seeded sample of its flattened elements (the same positions in every run), so two builds compare output for output."""
+    arrays = {"loss": loss.detach()}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach()
+    cap = (DUMP_BUDGET_BYTES - (1 << 20)) // 4 // len(arrays)      # elements per array (1 MB left for the .npy headers)
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:      # a dump directory made inside the tree stays out of git status
+            f.write("*\n")
+    total, sampled = 0, []
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))]
+            sampled.append(name)
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32, order="C"))
+        total += a.nbytes
+    return {"dir": os.path.abspath(path), "arrays": len(arrays), "bytes": total, "sampled": sampled}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -265,7 +293,11 @@ def main():
                          "process shows that RCCL capture works on this machine (auto), or keep the two-graph form around an eager all-reduce (off)")
     ap.add_argument("--chains", type=int, default=int(os.environ.get("STGCN_CHAINS", "1")),
                     help="micro-batch chains of the minibatch run concurrently on separate HIP streams (train.chained_fwd_bwd)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, parameters and gradients of the last timed step as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     DTYPE = args.dtype or cfg["dtype"]
     cfg["workload"] = cfg["workload"].format(dtype="fp32" if DTYPE == "f32" else "bf16")
@@ -381,6 +413,8 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
+    # (before anything below steps the same model again: the secondary measurements and the profile pass keep training it)
+    dumped = dump_outputs(args.dump_outputs, loss, model) if (args.dump_outputs and rank == 0) else None
     loss_val = float(loss.item())
     from stgcn_amd.train import check_in_launch_waits
     check_in_launch_waits(model)      # (after the timed region: a starved in-launch wait would have made the loss NaN -- this says where)
@@ -411,6 +445,7 @@ def main():
                       "output_block": "fused HIP path (stgcn_outblock_*)", "final_loss": round(loss_val, 5),
                       "launch": "hipGraph replay" if use_graph else "eager", "graph_error": graph_err,
                       **({"replay_ms": replay_ms} if replay_ms else {}),
+                      **({"dumped_outputs": dumped} if dumped else {}),
                       "chains": args.chains if use_graph else 1,
                       "backward_products": ("bf16" if DTYPE == "bf16" else args.bwd_precision),
                       **({"matrix_products": ("fp32 in, fp32 accumulate; tc1_fwd / tc2_ln_fwd / tc1_bwd form their products as bf16x6 -- both operands split EXACTLY into "
