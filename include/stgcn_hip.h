@@ -30,9 +30,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6).  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7).  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
-#define STGCN_ABI_VERSION 6
+#define STGCN_ABI_VERSION 7
 
 #define STGCN_OK 0
 #define STGCN_ERR_UNSUPPORTED 1 /* shape outside what the kernels cover (message says which) */
@@ -450,6 +450,33 @@ typedef struct stgcn_adamw_hyper {
 int stgcn_grad_flush(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
                      const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count,
                      const stgcn_adamw_hyper* hyper, void* stream);
+
+/* ---- The reference's other optimizers (main.py:149-154, --opt): one hyper-parameter block for every kind.
+ *        STGCN_OPT_ADAMW   torch.optim.AdamW, as stgcn_adamw_step (momentum_decay, mu_product* unused)
+ *        STGCN_OPT_NADAMW  torch.optim.NAdam(lr, betas, eps, weight_decay, momentum_decay, decoupled_weight_decay=True) (main.py:150)
+ *        STGCN_OPT_LION    script/opt.py Lion(lr, betas, weight_decay) (main.py:152); one state tensor: exp_avg_sq may be NULL, eps unused
+ *      step / step_dev / lr_dev as for stgcn_adamw_step (lr_dev is fp32).  NAdamW's running product mu_1 * ... * mu_{t-1} enters as mu_product
+ *      (eager: the caller keeps it) or, when mu_product_dev is set, from two DEVICE floats used by step parity: the launch reads
+ *      mu_product_dev[(t-1) & 1] and writes mu_product_dev[t & 1] = that * mu_t (initialise both to 1 for t = 0), so a captured
+ *      hipGraph advances it without a host round trip.  Exactly one update launch per step count t.                          */
+#define STGCN_OPT_ADAMW 0
+#define STGCN_OPT_NADAMW 1
+#define STGCN_OPT_LION 2
+typedef struct stgcn_optim_hyper {
+    int32_t kind;
+    double lr, beta1, beta2, eps, weight_decay, momentum_decay;   /* as the caller holds them; fp32 factors such as 1 - beta1 are formed from these */
+    int64_t step;
+    const int64_t* step_dev;
+    const float* lr_dev;
+    float mu_product;
+    float* mu_product_dev;
+} stgcn_optim_hyper;
+/* optimizer.step() for any kind: the multi-tensor update of stgcn_adamw_step (AdamW takes that very launch) */
+int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, void* stream);
+/* stgcn_grad_flush with the optimizer of `hyper` applied to each freshly reduced gradient element (AdamW: that very launch) */
+int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                           const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count,
+                           const stgcn_optim_hyper* hyper, void* stream);
 
 /* ---- Loss: nn.MSELoss() as main.py:136 builds it (mean over all n = B*N elements) together with the gradient that
  *      l.backward() (main.py:168) feeds into the model output, in one launch:

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libstgcn_hip.so")
 
 STGCN_OK = 0
-ABI_VERSION = 6      # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
+ABI_VERSION = 7      # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
 ACT = {"glu": 0, "gtu": 1}
 GRAPH_CONV = {"cheb_graph_conv": 0, "graph_conv": 1}
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -115,6 +115,15 @@ class AdamwHyper(C.Structure):        # stgcn_adamw_hyper
                 ("step", C.c_int64), ("step_dev", C.c_void_p), ("lr_dev", C.c_void_p)]
 
 
+OPT_ADAMW, OPT_NADAMW, OPT_LION = 0, 1, 2      # STGCN_OPT_*
+
+
+class OptimHyper(C.Structure):        # stgcn_optim_hyper
+    _fields_ = [("kind", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("momentum_decay", C.c_double), ("step", C.c_int64), ("step_dev", C.c_void_p),
+                ("lr_dev", C.c_void_p), ("mu_product", C.c_float), ("mu_product_dev", C.c_void_p)]
+
+
 class StgcnError(RuntimeError):
     pass
 
@@ -205,6 +214,11 @@ class _Lib:
         d.stgcn_grad_flush.argtypes = [C.c_int32, C.POINTER(FlushBlock), C.POINTER(OutblockDesc), C.POINTER(OutblockGrads), C.c_void_p,
                                        C.POINTER(AdamwTensor), C.c_int32, C.POINTER(AdamwHyper), C.c_void_p]
         d.stgcn_grad_flush.restype = C.c_int
+        d.stgcn_optim_step.argtypes = [C.POINTER(AdamwTensor), C.c_int32, C.POINTER(OptimHyper), C.c_void_p]
+        d.stgcn_optim_step.restype = C.c_int
+        d.stgcn_grad_flush_optim.argtypes = [C.c_int32, C.POINTER(FlushBlock), C.POINTER(OutblockDesc), C.POINTER(OutblockGrads), C.c_void_p,
+                                             C.POINTER(AdamwTensor), C.c_int32, C.POINTER(OptimHyper), C.c_void_p]
+        d.stgcn_grad_flush_optim.restype = C.c_int
         d.stgcn_mse_loss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p]
         d.stgcn_mse_loss_grad.restype = C.c_int
@@ -253,4 +267,5 @@ EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn
                     "stgcn_set_gc_precision", "stgcn_set_gc_ld_pad", "stgcn_set_debug_stages",
                     "stgcn_stblock_ln_hook", "stgcn_stblock_backward_hook", "stgcn_outblock_backward_hook", "stgcn_set_tc1_bwd_wgs",
                     "stgcn_set_slab_gc_precision", "stgcn_outblock_backward_loss", "stgcn_set_bwd_precision", "stgcn_set_gemm_big_nt",
-                    "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush"]
+                    "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush",
+                    "stgcn_optim_step", "stgcn_grad_flush_optim"]

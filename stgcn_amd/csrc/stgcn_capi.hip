@@ -988,7 +988,22 @@ int launch_reduce_list(const char* label, ReduceList& L, hipStream_t st) {
             fprintf(stderr, "[stgcn reduce] %s job %d: %ld elements x %d partials (%.2f MB read), %d workgroups\n", label, i,
                     (long)j.n0 * j.n1 * j.n2, j.P, 4e-6 * (double)j.n0 * j.n1 * j.n2 * j.P, L.ra.start[i + 1] - L.ra.start[i]);
         }
-    STGCN_LAUNCH(label, st, reduce_kernel, dim3(L.ra.start[L.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), L.ra);
+    STGCN_LAUNCH(label, st, reduce_kernel<kOptAdamw>, dim3(L.ra.start[L.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), L.ra);
+    return STGCN_OK;
+}
+// the same job list with the NAdamW / Lion epilogue (stgcn_grad_flush_optim)
+int launch_reduce_list_optim(const char* label, ReduceList& L, int kind, const OptimExtra& x, hipStream_t st) {
+    if (L.overflow) return fail(STGCN_ERR_INVALID, "%s: more than %d reduction jobs in one launch", label, kMaxReduceJobs);
+    if (L.nj == 0) return STGCN_OK;
+    L.ra.njobs = L.nj;
+    ReduceOptimArgs a;
+    memset(&a, 0, sizeof(a));
+    static_cast<ReduceArgs&>(a) = L.ra;
+    a.x = x;
+    if (kind == kOptNadamw)
+        STGCN_LAUNCH(label, st, reduce_kernel<kOptNadamw>, dim3(L.ra.start[L.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), a);
+    else
+        STGCN_LAUNCH(label, st, reduce_kernel<kOptLion>, dim3(L.ra.start[L.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), a);
     return STGCN_OK;
 }
 void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const Derived& v, const BwdGeom& bg, const float* part,

@@ -539,6 +539,65 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
     reduce_jobs_head(RL, d, g, part, ws + pl.ws_dyln, G);
     return launch_reduce_list("head.reduce", RL, st);
 }
+// the job list of a whole-model flush with the optimizer table attached (stgcn_grad_flush, stgcn_grad_flush_optim); need_v: the kind keeps
+// exp_avg_sq (every kind but Lion)
+int flush_job_list(ReduceList& RL, const char* who, int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                   const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count, bool need_v) {
+    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "%s: bad block table", who);
+    for (int i = 0; i < n_blocks; ++i) {
+        const stgcn_stblock_desc* d = blocks[i].desc;
+        stgcn_stblock_plan pl;
+        int rc = stgcn_stblock_plan_query(d, &pl);
+        if (rc) return rc;
+        if (!blocks[i].grads || !blocks[i].ws) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in block %d", who, i);
+        const Derived v = derive(d);
+        const BwdGeom bg = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
+        reduce_jobs_block(RL, d, v, bg, blocks[i].ws + pl.ws_part, blocks[i].grads);
+    }
+    if (head_desc) {
+        stgcn_outblock_plan pl;
+        int rc = stgcn_outblock_plan_query(head_desc, &pl);
+        if (rc) return rc;
+        if (!head_grads || !head_ws) return fail(STGCN_ERR_INVALID, "%s: NULL head pointer", who);
+        const HeadGeom g = head_geom(head_desc);
+        reduce_jobs_head(RL, head_desc, g, head_ws + pl.ws_part, head_ws + pl.ws_dyln, head_grads);
+    }
+    if (opt_count > 0) {
+        int matched = 0;
+        for (int k = 0; k < RL.nj; ++k)
+            for (int i = 0; i < opt_count; ++i)
+                if (opt[i].grad == RL.ra.job[k].dst) {
+                    if (!opt[i].param || !opt[i].exp_avg || (need_v && !opt[i].exp_avg_sq)) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in optimizer entry %d", who, i);
+                    RL.ra.job[k].p = opt[i].param; RL.ra.job[k].m = opt[i].exp_avg; RL.ra.job[k].v = opt[i].exp_avg_sq;
+                    if (((reinterpret_cast<uintptr_t>(opt[i].param) | reinterpret_cast<uintptr_t>(opt[i].exp_avg) | reinterpret_cast<uintptr_t>(opt[i].exp_avg_sq)) & 15) != 0)
+                        RL.ra.job[k].dvec = 0;   // (the 16-byte form of the state update needs aligned state tensors)
+                    ++matched;
+                    break;
+                }
+        if (matched != opt_count) return fail(STGCN_ERR_INVALID, "%s: %d of %d optimizer entries have no gradient in this flush", who, opt_count - matched, opt_count);
+    }
+    return STGCN_OK;
+}
+
+// NAdamW / Lion constants beyond ReduceArgs / AdamwArgs, formed in double like torch forms them
+OptimExtra optim_extra(const stgcn_optim_hyper* h) {
+    OptimExtra x;
+    memset(&x, 0, sizeof(x));
+    x.omb1 = (float)(1.0 - h->beta1);
+    x.omb2 = (float)(1.0 - h->beta2);
+    x.mu_k = (float)(h->momentum_decay * log(0.96));
+    x.mu_prod = h->mu_product;
+    x.mu_dev = h->kind == STGCN_OPT_NADAMW ? h->mu_product_dev : nullptr;
+    x.mu_job = -1;
+    return x;
+}
+int check_optim_hyper(const stgcn_optim_hyper* h, const char* who) {
+    if (!h) return fail(STGCN_ERR_INVALID, "%s: NULL hyper-parameters", who);
+    if (h->kind != STGCN_OPT_ADAMW && h->kind != STGCN_OPT_NADAMW && h->kind != STGCN_OPT_LION)
+        return fail(STGCN_ERR_INVALID, "%s: unknown optimizer kind %d", who, (int)h->kind);
+    return STGCN_OK;
+}
+
 }  // namespace
 extern "C" {
 
@@ -573,46 +632,88 @@ int stgcn_grad_flush(int32_t n_blocks, const stgcn_flush_block* blocks, const st
                      const stgcn_adamw_hyper* hyper, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     defer_join(static_cast<hipStream_t>(stream));   // (the head's weight-gradient launch of this step, if it ran on the side stream)
-    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: bad block table");
     if (opt_count < 0 || (opt_count > 0 && (!opt || !hyper))) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: optimizer table without hyper-parameters");
     ReduceList RL;
-    for (int i = 0; i < n_blocks; ++i) {
-        const stgcn_stblock_desc* d = blocks[i].desc;
-        stgcn_stblock_plan pl;
-        int rc = stgcn_stblock_plan_query(d, &pl);
-        if (rc) return rc;
-        if (!blocks[i].grads || !blocks[i].ws) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: NULL pointer in block %d", i);
-        const Derived v = derive(d);
-        const BwdGeom bg = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
-        reduce_jobs_block(RL, d, v, bg, blocks[i].ws + pl.ws_part, blocks[i].grads);
-    }
-    if (head_desc) {
-        stgcn_outblock_plan pl;
-        int rc = stgcn_outblock_plan_query(head_desc, &pl);
-        if (rc) return rc;
-        if (!head_grads || !head_ws) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: NULL head pointer");
-        const HeadGeom g = head_geom(head_desc);
-        reduce_jobs_head(RL, head_desc, g, head_ws + pl.ws_part, head_ws + pl.ws_dyln, head_grads);
-    }
+    int rc = flush_job_list(RL, "stgcn_grad_flush", n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, true);
+    if (rc) return rc;
     if (opt_count > 0) {
-        int matched = 0;
-        for (int k = 0; k < RL.nj; ++k)
-            for (int i = 0; i < opt_count; ++i)
-                if (opt[i].grad == RL.ra.job[k].dst) {
-                    if (!opt[i].param || !opt[i].exp_avg || !opt[i].exp_avg_sq) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: NULL pointer in optimizer entry %d", i);
-                    RL.ra.job[k].p = opt[i].param; RL.ra.job[k].m = opt[i].exp_avg; RL.ra.job[k].v = opt[i].exp_avg_sq;
-                    if (((reinterpret_cast<uintptr_t>(opt[i].param) | reinterpret_cast<uintptr_t>(opt[i].exp_avg) | reinterpret_cast<uintptr_t>(opt[i].exp_avg_sq)) & 15) != 0)
-                        RL.ra.job[k].dvec = 0;   // (the 16-byte form of the state update needs aligned state tensors)
-                    ++matched;
-                    break;
-                }
-        if (matched != opt_count) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: %d of %d optimizer entries have no gradient in this flush", opt_count - matched, opt_count);
         RL.ra.lr = hyper->lr; RL.ra.b1 = hyper->beta1; RL.ra.b2 = hyper->beta2; RL.ra.eps = hyper->eps; RL.ra.wd = hyper->weight_decay;
         RL.ra.lb1 = (float)log((double)hyper->beta1); RL.ra.lb2 = (float)log((double)hyper->beta2);
         RL.ra.step = (long)hyper->step; RL.ra.step_dev = reinterpret_cast<const long*>(hyper->step_dev); RL.ra.lr_dev = hyper->lr_dev;
     }
     g_prof_tag = 0;
     return launch_reduce_list(opt_count > 0 ? "reduce_adamw" : "reduce_all", RL, (hipStream_t)stream);
+}
+
+int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, void* stream) {
+    int rc = check_optim_hyper(hyper, "stgcn_optim_step");
+    if (rc) return rc;
+    if (hyper->kind == STGCN_OPT_ADAMW)
+        return stgcn_adamw_step(tensors, count, (float)hyper->lr, (float)hyper->beta1, (float)hyper->beta2, (float)hyper->eps, (float)hyper->weight_decay,
+                                hyper->step, hyper->step_dev, hyper->lr_dev, stream);
+    STGCN_FLUSH_PENDING_PACK();
+    if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "stgcn_optim_step: bad tensor table");
+    const bool lion = hyper->kind == STGCN_OPT_LION;
+    hipStream_t st = (hipStream_t)stream;
+    for (int off = 0; off < count; off += kAdamwMaxTensors) {
+        AdamwArgs a;
+        memset(&a, 0, sizeof(a));
+        const int n = count - off < kAdamwMaxTensors ? count - off : kAdamwMaxTensors;
+        for (int i = 0; i < n; ++i) {
+            const stgcn_adamw_tensor& t = tensors[off + i];
+            if (!t.param || !t.grad || !t.exp_avg || (!lion && !t.exp_avg_sq) || t.numel < 0)
+                return fail(STGCN_ERR_INVALID, "stgcn_optim_step: NULL pointer in entry %d", off + i);
+            a.t[i].p = t.param; a.t[i].g = t.grad; a.t[i].m = t.exp_avg; a.t[i].v = lion ? nullptr : t.exp_avg_sq; a.t[i].n = (long)t.numel;
+            a.start[i + 1] = a.start[i] + cdiv(t.numel, kAdamwChunk);
+        }
+        a.count = n; a.lr = (float)hyper->lr; a.b1 = (float)hyper->beta1; a.b2 = (float)hyper->beta2; a.eps = (float)hyper->eps;
+        a.wd = (float)hyper->weight_decay; a.step = (long)hyper->step;
+        a.lb1 = (float)log(hyper->beta1); a.lb2 = (float)log(hyper->beta2);
+        a.step_dev = reinterpret_cast<const long*>(hyper->step_dev); a.lr_dev = hyper->lr_dev;
+        OptimExtra x = optim_extra(hyper);
+        int first = -1;   // the running product advances once per step: element 0 of the first non-empty tensor of the first launch
+        for (int i = 0; off == 0 && i < n && first < 0; ++i)
+            if (a.t[i].n > 0) first = i;
+        x.mu_job = first;
+        g_prof_tag = 0;
+        if (a.start[n] > 0) {
+            if (lion) STGCN_LAUNCH("lion", st, optim_kernel<kOptLion>, dim3(a.start[n]), dim3(kThreads), 0, a, x);
+            else STGCN_LAUNCH("nadamw", st, optim_kernel<kOptNadamw>, dim3(a.start[n]), dim3(kThreads), 0, a, x);
+        }
+    }
+    return STGCN_OK;
+}
+
+int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                           const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count,
+                           const stgcn_optim_hyper* hyper, void* stream) {
+    int rc = check_optim_hyper(hyper, "stgcn_grad_flush_optim");
+    if (rc) return rc;
+    if (hyper->kind == STGCN_OPT_ADAMW) {
+        stgcn_adamw_hyper h;
+        memset(&h, 0, sizeof(h));
+        h.lr = (float)hyper->lr; h.beta1 = (float)hyper->beta1; h.beta2 = (float)hyper->beta2; h.eps = (float)hyper->eps;
+        h.weight_decay = (float)hyper->weight_decay; h.step = hyper->step; h.step_dev = hyper->step_dev; h.lr_dev = hyper->lr_dev;
+        return stgcn_grad_flush(n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, &h, stream);
+    }
+    STGCN_FLUSH_PENDING_PACK();
+    defer_join(static_cast<hipStream_t>(stream));
+    if (opt_count < 1 || !opt) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_optim: empty optimizer table");
+    const bool lion = hyper->kind == STGCN_OPT_LION;
+    ReduceList RL;
+    rc = flush_job_list(RL, "stgcn_grad_flush_optim", n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, !lion);
+    if (rc) return rc;
+    if (RL.overflow) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_optim: more than %d reduction jobs in one launch", kMaxReduceJobs);
+    RL.ra.lr = (float)hyper->lr; RL.ra.b1 = (float)hyper->beta1; RL.ra.b2 = (float)hyper->beta2; RL.ra.eps = (float)hyper->eps;
+    RL.ra.wd = (float)hyper->weight_decay; RL.ra.lb1 = (float)log(hyper->beta1); RL.ra.lb2 = (float)log(hyper->beta2);
+    RL.ra.step = (long)hyper->step; RL.ra.step_dev = reinterpret_cast<const long*>(hyper->step_dev); RL.ra.lr_dev = hyper->lr_dev;
+    OptimExtra x = optim_extra(hyper);
+    for (int k = 0; k < RL.nj && x.mu_job < 0; ++k)      // the running product advances at element 0 of the first optimizer job
+        if (RL.ra.job[k].p && (long)RL.ra.job[k].n0 * RL.ra.job[k].n1 * RL.ra.job[k].n2 > 0) x.mu_job = k;
+    if (lion)
+        for (int k = 0; k < RL.nj; ++k) RL.ra.job[k].v = nullptr;
+    g_prof_tag = 0;
+    return launch_reduce_list_optim(lion ? "reduce_lion" : "reduce_nadamw", RL, hyper->kind, x, (hipStream_t)stream);
 }
 
 int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,

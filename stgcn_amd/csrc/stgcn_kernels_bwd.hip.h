@@ -1583,6 +1583,59 @@ __global__ __launch_bounds__(256 * kWgradGroups) void wgrad_pair_kernel(TconvBwd
 // loads, else 1 element); its slices (8, or 32 for jobs with >= 128 partials: the walk over p is a serial latency chain)
 // take the partials p = slice, slice+slices, .. and are combined through LDS in a fixed order (bitwise reproducible).
 // ================================================================================================
+// ---- Optimizer kinds of the fused step tail and of the multi-tensor step (= STGCN_OPT_* of stgcn_hip.h) ------------------
+// AdamW keeps its own arithmetic inline (reduce_kernel<kOptAdamw>, adamw_kernel).  NAdamW (torch.optim.NAdam with decoupled decay,
+// main.py:150) and Lion (script/opt.py, main.py:152) update one element with the functions below, shared by reduce_kernel<KIND> and
+// optim_kernel<KIND>; they restate torch's fp32 CPU arithmetic op by op (contraction off, fmaf exactly where ATen's vector kernels fuse:
+// add with alpha, lerp, addcmul), so that Lion's sign(c) agrees element for element with the reference's.
+enum { kOptAdamw = 0, kOptNadamw = 1, kOptLion = 2 };
+struct OptimExtra {
+    float omb1, omb2;   // 1 - beta1, 1 - beta2 rounded from double on the host (the factors torch forms)
+    float mu_k;         // NAdamW: momentum_decay * log(0.96), mu_t = beta1 (1 - 0.5 exp(t mu_k))
+    float mu_prod;      // NAdamW eager: mu_1 ... mu_{t-1} (the host keeps the product)
+    float* mu_dev;      // NAdamW capturable: two device slots used by step parity; the launch reads [(t-1)&1], one thread writes [t&1]
+    int mu_job;         // the job / tensor whose element 0 writes mu_dev[t&1]; -1: none (later launches of a split table)
+};
+struct OptimScalars {   // per step, identical in every thread
+    float decay, lr;
+    float rbc2, cg, cm;  // NAdamW: 1 - beta2^t, the coefficients of g/d and m/d
+    float mu_prod;       // NAdamW: mu_1 ... mu_t (what the writer stores)
+};
+template <int KIND>
+__device__ __forceinline__ OptimScalars optim_scalars(float t, float lr, float b1, float lb2, float wd, const OptimExtra& x) {
+#pragma clang fp contract(off)
+    OptimScalars s;
+    s.lr = lr;
+    s.decay = fmaf(-lr, wd, 1.0f);
+    s.rbc2 = s.cg = s.cm = s.mu_prod = 0.f;
+    if (KIND == kOptNadamw) {
+        const float mu = b1 * (1.0f - 0.5f * expf(t * x.mu_k)), mu_next = b1 * (1.0f - 0.5f * expf((t + 1.0f) * x.mu_k));
+        const float prev = x.mu_dev ? x.mu_dev[((long)t - 1) & 1] : x.mu_prod;
+        s.mu_prod = prev * mu;
+        s.rbc2 = -expm1f(t * lb2);
+        s.cg = -lr * (1.0f - mu) / (1.0f - s.mu_prod);
+        s.cm = -lr * mu_next / (1.0f - s.mu_prod * mu_next);
+    }
+    return s;
+}
+__device__ __forceinline__ void nadamw_element(float g, float& p, float& m, float& v, float b2, float eps, const OptimScalars& s, const OptimExtra& x) {
+#pragma clang fp contract(off)
+    const float pd = p * s.decay;
+    m = fmaf(x.omb1, g - m, m);                  // exp_avg.lerp_(grad, 1 - beta1)
+    v = fmaf(x.omb2 * g, g, v * b2);             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    const float d = sqrtf(v / s.rbc2) + eps;
+    const float p1 = pd + (s.cg * g) / d;        // param.addcdiv_(grad, denom, value=cg)
+    p = p1 + (s.cm * m) / d;                     // param.addcdiv_(exp_avg, denom, value=cm)
+}
+__device__ __forceinline__ void lion_element(float g, float& p, float& m, float b1, float b2, const OptimScalars& s, const OptimExtra& x) {
+#pragma clang fp contract(off)
+    const float pd = p * s.decay;
+    const float c = m * b1 + g * x.omb1;         // exp_avg * beta1 + grad * (1 - beta1): two roundings, then the sum
+    const float sg = c > 0.f ? 1.0f : (c < 0.f ? -1.0f : 0.0f);
+    p = pd - s.lr * sg;
+    m = fmaf(g, x.omb2, m * b2);                 // exp_avg.mul_(beta2).add_(grad, alpha=1 - beta2)
+}
+
 struct ReduceJob {
     const float* src;
     float* dst;
@@ -1610,6 +1663,12 @@ struct ReduceArgs {
     const long* step_dev;
     const float* lr_dev;
 };
+struct ReduceOptimArgs : ReduceArgs {   // the NAdamW / Lion instantiations: AdamW's launch arguments stay exactly ReduceArgs
+    OptimExtra x;
+};
+static_assert(sizeof(ReduceOptimArgs) <= 4096, "reduce_kernel arguments exceed 4 KiB");
+template <int KIND> struct ReduceArgsOf { typedef ReduceOptimArgs type; };
+template <> struct ReduceArgsOf<kOptAdamw> { typedef ReduceArgs type; };
 // host: classify the job and return its workgroup count
 // element count from which a table takes the big-table forms below (STGCN_REDUCE_BIG: the emulator tests force them on small models)
 inline long reduce_big_threshold() {
@@ -1629,7 +1688,9 @@ inline int reduce_job_setup(ReduceJob& j) {
     return (int)((n + per - 1) / per);
 }
 
-__global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a) {
+// KIND: the optimizer of the fused epilogue (jobs with p != null); kOptAdamw is also the plain reduction (no job has p)
+template <int KIND>
+__global__ __launch_bounds__(256) void reduce_kernel(typename ReduceArgsOf<KIND>::type a) {
     extern __shared__ float stgcn_smem[];   // [slices][32] float4
     int jb = 0;
     while (jb + 1 < a.njobs && (int)blockIdx.x >= a.start[jb + 1]) ++jb;
@@ -1655,13 +1716,13 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a) {
             lr = a.lr_dev ? *a.lr_dev : a.lr;
             if (j.dvec) {
                 om = ld4(j.m + doff);
-                ov = ld4(j.v + doff);
+                if (KIND != kOptLion) ov = ld4(j.v + doff);     // (Lion has no second moment)
                 op = ld4(j.p + doff);
             } else
             for (int i = 0; i < nw; ++i) {
                 const long o = doff + (long)i * j.t2;
                 om[i] = j.m[o];
-                ov[i] = j.v[o];
+                if (KIND != kOptLion) ov[i] = j.v[o];
                 op[i] = j.p[o];
             }
         }
@@ -1696,6 +1757,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a) {
         if (j.dvec) st4(j.dst + doff, t);
         else
             for (int i = 0; i < nw; ++i) j.dst[doff + (long)i * j.t2] = t[i];
+        if constexpr (KIND == kOptAdamw) {
         if (j.p) {   // AdamW on the freshly reduced gradient (torch.optim.AdamW, see adamw_kernel)
             const float bc1 = -expm1f(ts * a.lb1);
             const float rs2 = rsqrtf(-expm1f(ts * a.lb2));
@@ -1718,6 +1780,28 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a) {
                     j.v[o] = nv[i];
                     j.p[o] = np_[i];
                 }
+        }
+        } else if (j.p) {   // NAdamW / Lion on the freshly reduced gradient (same element functions as optim_kernel)
+            const OptimScalars s = optim_scalars<KIND>(ts, lr, a.b1, a.lb2, a.wd, a.x);
+            for (int i = 0; i < nw; ++i) {
+                float pp = op[i], mm = om[i], vv = ov[i];
+                if (KIND == kOptNadamw) nadamw_element(t[i], pp, mm, vv, a.b2, a.eps, s, a.x);
+                else lion_element(t[i], pp, mm, a.b1, a.b2, s, a.x);
+                op[i] = pp; om[i] = mm; ov[i] = vv;
+            }
+            if (j.dvec) {
+                st4(j.m + doff, om);
+                if (KIND != kOptLion) st4(j.v + doff, ov);
+                st4(j.p + doff, op);
+            } else
+                for (int i = 0; i < nw; ++i) {
+                    const long o = doff + (long)i * j.t2;
+                    j.m[o] = om[i];
+                    if (KIND != kOptLion) j.v[o] = ov[i];
+                    j.p[o] = op[i];
+                }
+            // NAdamW under capture: element 0 of the designated job advances the running product (the other slot than every thread read)
+            if (KIND == kOptNadamw && a.x.mu_dev && jb == a.x.mu_job && e == 0) a.x.mu_dev[(long)ts & 1] = s.mu_prod;
         }
     }
 }

@@ -319,6 +319,38 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a) {
 }
 
 // ================================================================================================
+// Multi-tensor NAdamW / Lion (main.py:150 / :152): adamw_kernel's table and chunking, the per-element arithmetic of
+// nadamw_element / lion_element (stgcn_kernels_bwd.hip.h, shared with the fused epilogue of reduce_kernel<KIND>).
+// Lion has no exp_avg_sq: T.v is never touched.  NAdamW's running product mu_1..mu_t: see OptimExtra.
+// ================================================================================================
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_kernel(AdamwArgs a, OptimExtra x) {
+    int jb = 0;
+    while (jb + 1 < a.count && (int)blockIdx.x >= a.start[jb + 1]) ++jb;
+    const AdamwTensor& T = a.t[jb];
+    const long base = ((long)blockIdx.x - a.start[jb]) * kAdamwChunk;
+    const float t = (float)(a.step_dev ? *a.step_dev : a.step);
+    const OptimScalars s = optim_scalars<KIND>(t, a.lr_dev ? *a.lr_dev : a.lr, a.b1, a.lb2, a.wd, x);
+#pragma unroll
+    for (int k = 0; k < kAdamwChunk / kThreads; ++k) {
+        const long e = base + k * kThreads + threadIdx.x;
+        if (e < T.n) {
+            float p = T.p[e], m = T.m[e];
+            if (KIND == kOptNadamw) {
+                float v = T.v[e];
+                nadamw_element(T.g[e], p, m, v, a.b2, a.eps, s, x);
+                T.v[e] = v;
+            } else {
+                lion_element(T.g[e], p, m, a.b1, a.b2, s, x);
+            }
+            T.m[e] = m;
+            T.p[e] = p;
+            if (KIND == kOptNadamw && x.mu_dev && jb == x.mu_job && e == 0) x.mu_dev[(long)t & 1] = s.mu_prod;
+        }
+    }
+}
+
+// ================================================================================================
 // nn.MSELoss() (main.py:136, mean over all B*N elements) and its gradient in ONE launch:
 //     loss = mean((pred - y)^2) ;  dpred = 2 (pred - y) * grad_scale / n
 // The reference's loss + l.backward() head is 5 ATen launches (mse, mean, ones_like fill, mse_backward, scale) for 6624

@@ -337,8 +337,8 @@ class GradSink:
     backward calls leave their per-workgroup gradient partials in the module workspaces, write NO parameter gradients and
     return none to autograd; ``flush()`` then reduces the partials of every module of the step in ONE launch straight into
     the sink's persistent gradient buffers (``grads[param]``, e.g. views of one flat data-parallel all-reduce buffer, which
-    the trainer also installs as ``param.grad``), optionally applying AdamW to each element as it is produced.  Three
-    reduce launches + the optimizer launch of a step become one."""
+    the trainer also installs as ``param.grad``), optionally applying the optimizer (AdamW; NAdamW / Lion through
+    ``stgcn_grad_flush_optim``) to each element as it is produced.  Three reduce launches + the optimizer launch of a step become one."""
 
     def __init__(self, grads: Dict[torch.nn.Parameter, torch.Tensor]):
         self.by_ptr = {p.data_ptr(): g for p, g in grads.items()}
@@ -352,7 +352,7 @@ class GradSink:
     def grad_for(self, p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         return None if p is None else self.by_ptr.get(p.data_ptr())
 
-    def flush(self, opt_table=None, hyper: Optional[AdamwHyper] = None, stream: Optional[int] = None) -> None:
+    def flush(self, opt_table=None, hyper: Optional[AdamwHyper | _lib.OptimHyper] = None, stream: Optional[int] = None) -> None:
         L = _lib.lib()
         arr = (FlushBlock * max(len(self.blocks), 1))()
         for i, (desc, gst, ws, _) in enumerate(self.blocks):
@@ -361,8 +361,12 @@ class GradSink:
         if self.head is not None:
             hd, hg, hws = C.byref(self.head[0]), C.byref(self.head[1]), self.head[2].data_ptr()
         n_opt = 0 if opt_table is None else len(opt_table)
-        L.check(L.dll.stgcn_grad_flush(len(self.blocks), arr, hd, hg, hws, opt_table, n_opt, None if hyper is None else C.byref(hyper), stream),
-                "stgcn_grad_flush")
+        if isinstance(hyper, _lib.OptimHyper):
+            L.check(L.dll.stgcn_grad_flush_optim(len(self.blocks), arr, hd, hg, hws, opt_table, n_opt, C.byref(hyper), stream),
+                    "stgcn_grad_flush_optim")
+        else:
+            L.check(L.dll.stgcn_grad_flush(len(self.blocks), arr, hd, hg, hws, opt_table, n_opt, None if hyper is None else C.byref(hyper), stream),
+                    "stgcn_grad_flush")
         self.blocks, self.head = [], None
         for o in self.owners:
             o.pending_sink = None

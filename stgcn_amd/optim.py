@@ -7,11 +7,16 @@ decay, no state).  It subclasses ``torch.optim.Optimizer`` so LR schedulers (Ste
 
 ``capturable=True`` keeps the step count and the learning rate in device memory so that ``step()`` can be
 recorded into a hipGraph; call ``sync_lr()`` after a scheduler changed ``param_groups[i]['lr']``.
+
+``NAdamW`` and ``Lion`` are the reference's two other optimizers (main.py:149-154, ``--opt nadamw | lion``) with the same
+surface: one HIP launch per ``step()`` (``stgcn_optim_step``) and the fused step tail (``flush_with`` through
+``stgcn_grad_flush_optim``).
 """
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -22,6 +27,9 @@ class AdamW(torch.optim.Optimizer):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._init_common(capturable)
+
+    def _init_common(self, capturable):
         self.capturable = capturable
         self._dev = {}     # per group: (step tensor, lr tensor) on the device (capturable mode)
         self.trainer_owns_step = False   # a trainer advances the device step count itself (stgcn_prepack counters): step() must not
@@ -57,24 +65,44 @@ class AdamW(torch.optim.Optimizer):
                 raise RuntimeError("stgcn_amd.optim.AdamW handles contiguous float32 parameters only")
             st = self.state[p]
             if not st:
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._init_state(st, p)
             table[i].param, table[i].grad = p.data_ptr(), grads[p].data_ptr()
-            table[i].exp_avg, table[i].exp_avg_sq, table[i].numel = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-        hyper = _lib.AdamwHyper()
-        b1, b2 = group["betas"]
-        hyper.lr, hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay = float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])
+            table[i].exp_avg, table[i].exp_avg_sq, table[i].numel = st["exp_avg"].data_ptr(), self._v_ptr(st), p.numel()
         if self.capturable and dev.type == "cuda":
             self.device_step_counter(dev)
             step_t, lr_t = self._dev[0]
             if bump_step:
                 step_t.add_(1)
-            hyper.step, hyper.step_dev, hyper.lr_dev = 0, step_t.data_ptr(), lr_t.data_ptr()
+            hyper = self._hyper(group, 0, step_t.data_ptr(), lr_t.data_ptr(), 0)
         else:
             group["_step"] = group.get("_step", 0) + 1
-            hyper.step, hyper.step_dev, hyper.lr_dev = group["_step"], None, None
+            hyper = self._hyper(group, group["_step"], None, None, 0)
         stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
         sink.flush(table, hyper, stream)
+        self._advance_host(group, hyper)
+
+    # ---- what the optimizer kinds differ in (state tensors, hyper-parameter block, launch) ------------------------------------------
+    def _init_state(self, st, p):
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _v_ptr(self, st):
+        return st["exp_avg_sq"].data_ptr()
+
+    def _hyper(self, group, step, step_dev, lr_dev, gi):
+        hyper = _lib.AdamwHyper()
+        b1, b2 = group["betas"]
+        hyper.lr, hyper.beta1, hyper.beta2, hyper.eps, hyper.weight_decay = float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])
+        hyper.step, hyper.step_dev, hyper.lr_dev = step, step_dev, lr_dev
+        return hyper
+
+    def _advance_host(self, group, hyper):
+        """after a launch: host-side state that eager mode keeps (none for AdamW)"""
+
+    def _launch_step(self, L, table, count, group, step, step_dev, lr_dev, gi, stream):
+        b1, b2 = group["betas"]
+        L.check(L.dll.stgcn_adamw_step(table, count, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                       float(group["weight_decay"]), step, step_dev, lr_dev, stream), "stgcn_adamw_step")
 
     def state_dict(self):
         """torch's state_dict plus the step counts, which capturable mode keeps in device tensors outside ``state`` (without them a
@@ -114,8 +142,7 @@ class AdamW(torch.optim.Optimizer):
                     raise RuntimeError("stgcn_amd.optim.AdamW handles contiguous float32 parameters only")
                 st = self.state[p]
                 if not st:
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    self._init_state(st, p)
             step_dev = lr_dev = None
             if self.capturable and dev.type == "cuda":
                 if gi not in self._dev:
@@ -132,9 +159,89 @@ class AdamW(torch.optim.Optimizer):
             for i, p in enumerate(live):
                 st = self.state[p]
                 table[i].param, table[i].grad = p.data_ptr(), p.grad.data_ptr()
-                table[i].exp_avg, table[i].exp_avg_sq, table[i].numel = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                table[i].exp_avg, table[i].exp_avg_sq, table[i].numel = st["exp_avg"].data_ptr(), self._v_ptr(st), p.numel()
             stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
-            b1, b2 = group["betas"]
-            L.check(L.dll.stgcn_adamw_step(table, len(live), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                           float(group["weight_decay"]), step, step_dev, lr_dev, stream), "stgcn_adamw_step")
+            self._launch_step(L, table, len(live), group, step, step_dev, lr_dev, gi, stream)
         return loss
+
+
+class _OptimKind(AdamW):
+    """NAdamW / Lion: AdamW's surface (capturable step count and lr, ``sync_lr``, ``flush_with``, ``trainer_owns_step``, state_dict with the
+    step count) over the kind-generic entry points ``stgcn_optim_step`` / ``stgcn_grad_flush_optim``."""
+    KIND = -1
+
+    def __init__(self, params, defaults, capturable):
+        lr, (b1, b2), wd = defaults["lr"], defaults["betas"], defaults["weight_decay"]
+        if lr < 0.0 or defaults.get("eps", 0.0) < 0.0 or not 0.0 <= b1 < 1.0 or not 0.0 <= b2 < 1.0 or wd < 0.0:
+            raise ValueError(f"invalid {type(self).__name__} hyper-parameter")
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self._init_common(capturable)
+        self._mu = {}      # NAdamW, capturable: per group the two device slots of the running product mu_1 ... mu_t (step parity)
+
+    def _mu_slots(self, gi):
+        if gi not in self._mu:
+            self._mu[gi] = torch.ones(2, dtype=torch.float32, device=self._dev[gi][0].device)
+        return self._mu[gi]
+
+    def _hyper(self, group, step, step_dev, lr_dev, gi):
+        h = _lib.OptimHyper()
+        b1, b2 = group["betas"]
+        h.kind, h.lr, h.beta1, h.beta2 = self.KIND, float(group["lr"]), float(b1), float(b2)
+        h.eps, h.weight_decay, h.momentum_decay = float(group.get("eps", 0.0)), float(group["weight_decay"]), float(group.get("momentum_decay", 0.0))
+        h.step, h.step_dev, h.lr_dev = step, step_dev, lr_dev
+        h.mu_product = float(group.get("_mu_product", 1.0))
+        h.mu_product_dev = self._mu_slots(gi).data_ptr() if (self.KIND == _lib.OPT_NADAMW and step_dev) else None
+        return h
+
+    def _launch_step(self, L, table, count, group, step, step_dev, lr_dev, gi, stream):
+        h = self._hyper(group, step, step_dev, lr_dev, gi)
+        L.check(L.dll.stgcn_optim_step(table, count, C.byref(h), stream), "stgcn_optim_step")
+        self._advance_host(group, h)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        for gi, g in enumerate(sd["param_groups"]):
+            if gi in self._mu and "_step" in g:
+                g["_mu_product"] = float(self._mu[gi][int(g["_step"]) & 1].item())
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for gi, group in enumerate(self.param_groups):
+            if self.capturable and gi in self._dev and "_mu_product" in group:
+                self._mu_slots(gi).fill_(float(group["_mu_product"]))
+
+
+class NAdamW(_OptimKind):
+    """torch.optim.NAdam(lr, betas, eps, weight_decay, momentum_decay, decoupled_weight_decay=True) as main.py:150 builds it (amsgrad-free,
+    maximize False).  The running product of the momentum schedule mu_t = beta1 (1 - 0.5 * 0.96^(t * momentum_decay)) is an fp32 number on
+    the host in eager mode (``param_groups[i]['_mu_product']``, advanced like torch's state tensor) and two device floats in capturable mode,
+    read and advanced by the update launch itself (stgcn_hip.h, stgcn_optim_hyper)."""
+    KIND = _lib.OPT_NADAMW
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum_decay=4e-3, capturable=False):
+        if momentum_decay < 0.0:
+            raise ValueError("invalid NAdamW hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum_decay=momentum_decay), capturable)
+
+    def _advance_host(self, group, hyper):
+        if hyper.mu_product_dev:
+            return
+        t, b1, md = float(hyper.step), float(group["betas"][0]), float(group["momentum_decay"])
+        mu = b1 * (1.0 - 0.5 * (0.96 ** (t * md)))
+        group["_mu_product"] = float(np.float32(group.get("_mu_product", 1.0)) * np.float32(mu))     # torch: fp32 state tensor *= mu
+
+
+class Lion(_OptimKind):
+    """script/opt.py ``Lion(lr, betas=(0.9, 0.99), weight_decay)`` as main.py:152 builds it: p *= 1 - lr wd ; c = beta1 m + (1 - beta1) g ;
+    p -= lr sign(c) ; m = beta2 m + (1 - beta2) g.  One state tensor (``exp_avg``), no eps."""
+    KIND = _lib.OPT_LION
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.99), weight_decay=1e-2, capturable=False):
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay), capturable)
+
+    def _init_state(self, st, p):
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _v_ptr(self, st):
+        return None

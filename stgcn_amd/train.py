@@ -176,14 +176,19 @@ class FlatGradAllReduce:
 
 def make_optimizer(model: torch.nn.Module, lr: float = 1e-3, weight_decay: float = 1e-3, name: str = "adamw",
                    capturable: bool = False):
-    """main.py:147-154 (adamw is the default; nadamw is NAdam with decoupled decay).
+    """main.py:147-154 (adamw is the default; nadamw is NAdam with decoupled decay; lion is script/opt.py's Lion).  Each is one HIP
+    launch per step and rides in the fused step tail (``flush_with``).
     ``capturable``: keep the step counters on the device so that ``step()`` can live inside a hipGraph."""
     params = list(model.parameters())
     if name == "adamw":
         from .optim import AdamW        # one HIP kernel per step (stgcn_adamw_step)
         return AdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
     if name == "nadamw":
-        return torch.optim.NAdam(params, lr=lr, weight_decay=weight_decay, decoupled_weight_decay=True)
+        from .optim import NAdamW       # main.py:150 (stgcn_optim_step)
+        return NAdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
+    if name == "lion":
+        from .optim import Lion         # main.py:152
+        return Lion(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
     raise ValueError(f"ERROR: The {name} optimizer is undefined.")   # main.py:154
 
 

@@ -2,7 +2,7 @@
 """End-to-end run of the reference's main.py flow on the MI355X path with a synthetic METR-LA-shaped dataset
 (34 272 rows x 207 sensors, v = clip(55 + 10 sin(2 pi t / 288 + phi_n) + N(0, 3^2), 0, 80); the real
 vel.csv is not available offline): 70/15/15 split (main.py:108-114), z-score fitted on the training rows (main.py:116-119),
-12 -> n_pred windows (script/dataloader.py:32-47), STGCNChebGraphConv on the real METR-LA operator, MSE + AdamW(1e-3, 1e-3)
+12 -> n_pred windows (script/dataloader.py:32-47), STGCNChebGraphConv on the real METR-LA operator, MSE + AdamW (or --opt nadamw | lion)(1e-3, 1e-3)
 with StepLR(10, 0.95) per epoch (main.py:147-156), unshuffled minibatches of 32 (main.py:126-131), validation loss per epoch
 (script/utility.py:90-101), test MAE / RMSE / WMAPE at the end (script/utility.py:103-121).
 
@@ -10,7 +10,7 @@ The training loop is `GraphedTrainStep(series=...)`: the z-scored (time, N) trai
 captured step windows it in place.  One JSON line per epoch and one for the test metrics; a persistence forecast
 (y_hat = last observed value) on the same windows is printed beside them for scale.
 
-  python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272]
+  python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion]
 """
 import argparse
 import json
@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--n-pred", type=int, default=3)
     ap.add_argument("--rows", type=int, default=34272)
+    ap.add_argument("--opt", choices=("adamw", "nadamw", "lion"), default="adamw")     # main.py:59
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
@@ -61,7 +62,7 @@ def main():
     torch.manual_seed(42)
     model = models.STGCNChebGraphConv(args, BLOCKS, n).to(dev)
     DropoutStream.manual_seed(42)
-    opt = make_optimizer(model, lr=1e-3, weight_decay=1e-3, capturable=True)
+    opt = make_optimizer(model, lr=1e-3, weight_decay=1e-3, name=a.opt, capturable=True)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.95)
 
     series = torch.from_numpy(train.astype(np.float32)).to(dev)
