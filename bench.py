@@ -6,8 +6,13 @@ A "step" is the reference's loop body (main.py:165-169): zero_grad -> forward ->
 (weak scaling: global batch = 32 * n_gpus, BASELINE.json configs[3] at 8 GPUs).  Inputs are resident in
 HBM before the timed region.  Prints ONE JSON line (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype f32|bf16] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, --dump-outputs, the result line.
+--full adds everything else, after the timed steps: the secondary precisions of the C2 step (secondary_bwd_bf16x3, secondary_fp32_mfma),
+the per-kernel hipEvent pass (roofline), the stock PyTorch-ROCm step (gpu_baseline), the CPU oracle step (cpu_baseline), the C3 / C5 lines
+(side_configs) and, with N > 1, the all-reduce timed on its own (config.allreduce).  The --no-* switches below drop single parts of --full.
 
 --config (default c2 = the headline; the others are the remaining single-GPU entries of BASELINE.json `configs`):
   c2  METR-LA, 207 nodes, ChebConv Ks=3, bs 32, 12->12, fp32                      (configs[1] / [3])
@@ -195,8 +200,8 @@ def side_config(name, steps, warmup, timeout_s=420):
     process (its own library modes, model and captured graph), summarised for the headline line: value, step time, dtype, the dominant
     launch against its roofline, the CPU baseline of the same shapes."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup), "--no-gpu-baseline",
-           "--no-side-configs", "--cpu-budget", "10"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup), "--full",
+           "--no-gpu-baseline", "--no-side-configs", "--cpu-budget", "10"]
     t0 = time.perf_counter()
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, cwd=ROOT)
@@ -278,12 +283,15 @@ def main():
     ap.add_argument("--bwd-precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="matrix products of the backward kernels of fp32 blocks: exact fp32 MFMAs (default, the headline) or split-bf16 operands "
                          "(three bf16 MFMAs per product, ~2^-16 relative: inside the 1e-3 gradient bar, NOT fp32 arithmetic -- an opt-in mode)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurement of the bf16x3-backward mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-side-configs", action="store_true", help="c2 only: do not append the c3 / c5 (bf16) measurements as `side_configs`")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of timed CPU-baseline steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the secondary precisions, the per-kernel roofline pass, the GPU and CPU baselines, "
+                         "the c3 / c5 side configs and (N > 1) the all-reduce alone; a plain run measures the headline only")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements of the bf16x3-backward and fp32-MFMA modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-gpu-baseline", action="store_true", help="--full: skip gpu_baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel hipEvent pass (roofline)")
+    ap.add_argument("--no-side-configs", action="store_true", help="--full, c2 only: do not append the c3 / c5 (bf16) measurements as `side_configs`")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of timed CPU-baseline steps")
     ap.add_argument("--replay-times", action="store_true", help="diagnostic: config.replay_ms = GPU time of each of the first steps after a synchronisation")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--no-resident-series", action="store_true",
@@ -457,7 +465,7 @@ def main():
                       "input": (f"device-side windows (n_his 12, n_pred {N_PRED}) of a resident (time, N) series, batch position on the device"
                                 if (resident and use_graph) else "(num, 1, n_his, N) window tensors, one batch copied per step")}}
 
-    if world > 1:
+    if world > 1 and args.full:
         # the step's one collective, timed on its own: ~1 MB flat fp32 gradient buffer, latency-bound on xGMI
         flat = graphed.flat if (use_graph and graphed is not None and graphed.flat is not None) else torch.zeros(230000, device=dev)
         for _ in range(5):
@@ -495,7 +503,7 @@ def main():
                                                     "eager all-reduce (torch.distributed backend " + torch.distributed.get_backend() +
                                                     "; nccl = RCCL) between the two captured graphs of the step" if use_graph else "eager")}
 
-    if world == 1 and use_graph and resident and DTYPE == "f32" and args.bwd_precision == "fp32" and not args.no_secondary:
+    if args.full and world == 1 and use_graph and resident and DTYPE == "f32" and args.bwd_precision == "fp32" and not args.no_secondary:
         # secondary measurement, same run, same model and optimizer state: the step with the opt-in "bf16x3" backward products
         # (ops.set_bwd_precision; gradients stay inside the 1e-3 bar, tests/test_gpu_bf16.py).  NOT the headline: `value` above is exact fp32.
         graphed.close()
@@ -540,7 +548,7 @@ def main():
             out["config"]["secondary_fp32_mfma"] = {"error": repr(e)}
         finally:
             os.environ.pop("STGCN_MFMA_X6", None)
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # per-kernel durations with hipEvents on the launch stream, over the same K steps (second pass)
         # (eager launches: hipEvents cannot be recorded inside a graph replay; the kernels and shapes are the same)
         if graphed is not None:
@@ -599,16 +607,16 @@ def main():
             rl["stblock_compulsory_bytes"] = comp
             rl["stblock_fwd_bwd_frac"] = round(stblock_total / (tot_ms * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4)
             rl["stblock_hbm_frac"] = round(comp / (tot_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_gpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_gpu_baseline:
         out["gpu_baseline"] = gpu_baseline(model, gso_t, cfg, B_LOCAL, N, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if N <= 1024:
             out["cpu_baseline"] = cpu_baseline(gso_np, cfg, B_LOCAL, args.cpu_budget)
             out["cpu_baseline"]["reference_published"] = {"value": {"c2": 159.2, "c3": 79.5}.get(args.config), "unit": "windows/s",
                                                           "source": "BASELINE.md section 2: the unmodified reference loop on 8 vCPU (survey container), fp32"}
         else:   # 8192 nodes: one oracle step costs ~1 TFLOP of fp32 operator products on the host -- a bounded sample at bs 2, no thread probing
             out["cpu_baseline"] = cpu_baseline(gso_np, cfg, 2, args.cpu_budget, probe=False)
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_side_configs and not B_OVERRIDE:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_side_configs and not B_OVERRIDE:
         # the other single-GPU configurations of BASELINE.json, witnessed by the same invocation
         del model, opt
         torch.cuda.empty_cache()

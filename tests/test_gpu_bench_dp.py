@@ -17,7 +17,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, STGCN_BENCH_BACKEND="gloo", STGCN_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
-           "--no-cpu-baseline", "--no-gpu-baseline", "--no-profile"]
+           "--full", "--no-cpu-baseline", "--no-gpu-baseline", "--no-profile"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

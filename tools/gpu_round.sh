@@ -18,10 +18,10 @@ test)
     timeout 900 python -m pytest tests -m gpu -q --maxfail=30 -p no:cacheprovider ${PYTEST_ARGS:-} > $OUT/pytest_gpu.log 2>&1
     echo "pytest exit $?" >> $OUT/pytest_gpu.log; tail -4 $OUT/pytest_gpu.log ;;
 bench)
-    timeout 600 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-side-configs ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+    timeout 600 python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-side-configs ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
     echo "bench exit $?"; cat $OUT/bench.json ;;
 benchfull)
-    timeout 600 python bench.py --steps 200 --warmup 20 --no-side-configs ${BENCH_ARGS:-} > $OUT/bench_full.json 2> $OUT/bench_full.err
+    timeout 600 python bench.py --steps 200 --warmup 20 --full --no-side-configs ${BENCH_ARGS:-} > $OUT/bench_full.json 2> $OUT/bench_full.err
     echo "benchfull exit $?"; cat $OUT/bench_full.json ;;
 smoke)
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?"; tail -2 $OUT/smoke.log ;;

@@ -22,7 +22,7 @@ for N in 1 2 4 8; do
     if [ "$N" -eq 1 ]; then
         timeout 900 python bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-gpu-baseline --no-side-configs --no-secondary > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
     else
-        timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 200 --warmup 20 \
+        timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 200 --warmup 20 --full \
             --capture-collective ${STGCN_CAPTURE:-auto} > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
     fi
     echo "N=$N exit $?"
