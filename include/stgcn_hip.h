@@ -30,9 +30,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7).  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8).  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
-#define STGCN_ABI_VERSION 7
+#define STGCN_ABI_VERSION 8
 
 #define STGCN_OK 0
 #define STGCN_ERR_UNSUPPORTED 1 /* shape outside what the kernels cover (message says which) */
@@ -485,6 +485,30 @@ int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, co
  *      target + *target_index_dev * target_index_stride floats (nullable: labels taken from the resident series).        */
 int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
                         const int64_t* target_index_dev, int64_t target_index_stride, void* stream);
+
+/* ---- Evaluation: the sums behind script/utility.py:90-101 (evaluate_model: MSE in z-scored units) and :103-121 (evaluate_metric: MAE,
+ *      RMSE, WMAPE after the scaler's inverse transform), formed on the device, one launch per minibatch, into a caller-owned state of
+ *      STGCN_EVAL_STATE_WORDS fp64 words that a whole pass over a split shares:
+ *          state[0] = sum (pred - y)^2      state[1] = sum |d|      state[2] = sum d^2      state[3] = sum (y scale + mean)
+ *          state[4] = elements counted      state[5..7] reserved (6: ticket word)           state[8..] per-workgroup partial slabs
+ *      with d = (y - pred) * scale[node] (scale / mean: per node, the inverse of the z-score; both NULL = identity).  Hence
+ *          MSE = state[0] / state[4], MAE = state[1] / state[4], RMSE = sqrt(state[2] / state[4]), WMAPE = state[1] / state[3].
+ *      pred: B * N floats; target: the label rows, B rows of N floats.  Windows b < first_valid of the batch are not counted (the last,
+ *      overlapped batch of a split counts only its new windows).  Terms are fp32, sums fp64, the summation order is fixed (two passes over
+ *      the same data leave bit-identical states; no floating-point atomics).  Batches below 32768 elements run as one workgroup, larger
+ *      ones as up to 64 workgroups whose partial slabs the last arriver adds in index order (STGCN_EVAL_BIG=<elements> moves the
+ *      threshold: a test knob).
+ *      pos (nullable): STGCN_EVAL_POS_WORDS device words {first window of the batch, first_valid, batches done, reserved}.  When given,
+ *      first_valid must be 0 and is read from pos[1], the labels are read at target + pos[0] * target_stride, and the SAME launch
+ *      advances the words for the next batch of a split of num_windows >= B windows: batch k starts at min(k B, num_windows - B) and
+ *      counts from window k B on -- a captured batch walks through a resident series by itself and never reads past it.
+ *      Bind the same pos[0] as x_index_dev of the model's first block.
+ *      The arm entry zeroes state[0..7] and the position words: a pass is arm, K accumulate launches, one read of state[0..4].   */
+#define STGCN_EVAL_STATE_WORDS 264
+#define STGCN_EVAL_POS_WORDS 4
+int stgcn_eval_arm(double* state, int64_t* pos, void* stream);
+int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                          int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, void* stream);
 
 /* Built-in kernel timer (no reference counterpart; feeds bench.py's roofline object).  While enabled,
  * every kernel launch is bracketed by a hipEvent pair on the launch stream.  collect() synchronises on the

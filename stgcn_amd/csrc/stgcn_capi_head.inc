@@ -726,6 +726,51 @@ int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float
     return STGCN_OK;
 }
 
+// element count of a batch from which stgcn_eval_accumulate takes the partial-slab form (STGCN_EVAL_BIG, read per call: the tests force
+// either form on one shape -- 0 forces the slabs, a huge value the single workgroup)
+static long eval_big_threshold() {
+    const char* e = getenv("STGCN_EVAL_BIG");
+    return e ? atol(e) : 32768;
+}
+
+int stgcn_eval_arm(double* state, int64_t* pos, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    if (!state) return fail(STGCN_ERR_INVALID, "stgcn_eval_arm: state is NULL");
+    g_prof_tag = 0;
+    STGCN_LAUNCH("eval_arm", (hipStream_t)stream, eval_arm_kernel, dim3(1), dim3(64), 0, state, reinterpret_cast<long*>(pos));
+    return STGCN_OK;
+}
+
+int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                          int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    if (!state) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: state is NULL");
+    if (!pred || !target) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: NULL pred / target");
+    if (B < 1 || N < 1) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: n = B * N must be positive (B=%d, N=%d)", B, N);
+    if ((scale == nullptr) != (mean == nullptr)) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: scale and mean come together (both or neither)");
+    if (first_valid < 0 || first_valid >= B)
+        return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: first_valid=%lld outside [0, B=%d)", (long long)first_valid, B);
+    if (pos) {
+        if (first_valid != 0) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: with position words first_valid is read from them (pass 0)");
+        if (num_windows < B) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: %lld windows are fewer than one batch of %d", (long long)num_windows, B);
+        if (target_stride < 0) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: negative target stride");
+    }
+    EvalAccArgs a;
+    a.pred = pred; a.target = target; a.scale = scale; a.mean = mean; a.state = state;
+    a.pos = reinterpret_cast<long*>(pos);
+    a.tstride = (long)target_stride; a.first_valid = (long)first_valid; a.num = (long)num_windows;
+    a.B = B; a.N = N;
+    const long n = (long)B * N;
+    int wgs = 1;
+    if (n >= eval_big_threshold()) {
+        wgs = cdiv(n, 2 * kEvalThreads);
+        wgs = wgs < 2 ? 2 : (wgs > kEvalMaxWgs ? kEvalMaxWgs : wgs);
+    }
+    g_prof_tag = 0;
+    STGCN_LAUNCH("eval_acc", (hipStream_t)stream, eval_acc_kernel, dim3(wgs), dim3(kEvalThreads), (kEvalThreads / 64) * 4 * sizeof(double), a);
+    return STGCN_OK;
+}
+
 #ifdef STGCN_PHASE_TIMING
 // diagnostic build only: select which kernel stamps its phases, read the stamps back (host buffer of 4096*16 int64)
 int stgcn_debug_phase_select(int kid) {

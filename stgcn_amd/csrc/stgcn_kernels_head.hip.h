@@ -380,4 +380,132 @@ __global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* pred, 
     }
 }
 
+// ================================================================================================
+// Evaluation metrics of one minibatch, added into a device-resident state that a whole pass over a split shares
+// (script/utility.py:90-101 evaluate_model, :103-121 evaluate_metric), in ONE launch per batch:
+//     state[0] += sum (p - y)^2                 z-scored units (the validation loss)
+//     state[1] += sum |d| ; state[2] += sum d^2 ; d = (y - p) * scale[node]   (the inverse transform's mean cancels)
+//     state[3] += sum (y * scale[node] + mean[node])                           (WMAPE's denominator)
+//     state[4] += elements counted
+// over the windows b >= first_valid of the batch (the overlapped last batch of a split counts only its new windows).  Terms are formed in
+// fp32, sums are carried in fp64 (a split has ~10^6 elements).  The summation order is fixed: thread-strided walks, a butterfly over
+// the wave (fp64 travels through the 32-bit shuffles as two words), the wave sums in wave order.  Two forms, by grid size:
+//   * one workgroup adds its sums straight into the state;
+//   * G > 1 workgroups leave their four sums in the state's partial slabs (state[8 + 4 g ..]), and the LAST ARRIVER at the ticket word
+//     (state[6]) adds them up in g order -- never in arrival order, never with floating-point atomics.  Hand-off: plain slab stores by
+//     wave 0, drained, agent release, drained, relaxed ticket add; the workgroup that draws G - 1 takes an agent acquire and reads the
+//     slabs with the acquiring wave's own loads.  It re-arms the ticket (stgcn_eval_arm zeroes it before the first launch of a pass).
+// With `pos` (device words: [0] first window of the batch, [1] first_valid, [2] batches done) the launch reads its position from there
+// and ADVANCES it for the next batch: k -> k + 1, start = min(k B, num - B), first_valid = min(B, k B - start), so that a captured batch
+// needs no launches of its own to move on.  Every workgroup has read the words before it draws its ticket; the last arriver writes them.
+// ================================================================================================
+constexpr int kEvalThreads = 1024;
+constexpr int kEvalMaxWgs = 64;
+constexpr int kEvalHdr = 8;       // fp64 words ahead of the partial slabs: four sums, the count, a spare, the ticket word, a spare
+struct EvalAccArgs {
+    const float* pred;     // [B][N]
+    const float* target;   // label row of window 0 (row b of the batch: + (start + b) * tstride when pos is set, else + b * N)
+    const float* scale;    // [N] or null (identity)
+    const float* mean;     // [N] or null
+    double* state;
+    long* pos;             // nullable
+    long tstride;
+    long first_valid;      // used when pos is null
+    long num;              // windows of the split (pos only)
+    int B, N;
+};
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __shfl_xor((unsigned)u, m), hi = __shfl_xor((unsigned)(u >> 32), m);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
+
+__device__ __forceinline__ void eval_finish(const EvalAccArgs& a, long fv, long k) {   // one thread, after the sums of the batch are in
+    a.state[4] += (double)((a.B - fv) * (long)a.N);
+    if (a.pos) {
+        const long done = (k + 1) * a.B;
+        const long start = done < a.num - a.B ? done : a.num - a.B;
+        a.pos[0] = start;
+        a.pos[1] = done - start < a.B ? done - start : a.B;
+        a.pos[2] = k + 1;
+    }
+}
+
+__global__ __launch_bounds__(1024) void eval_acc_kernel(EvalAccArgs a) {
+    extern __shared__ float stgcn_smem[];
+    double* red = reinterpret_cast<double*>(stgcn_smem);   // [16 waves][4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long start = 0, fv = a.first_valid, k = 0;
+    if (a.pos) {
+        start = a.pos[0];
+        fv = a.pos[1];
+        k = a.pos[2];
+        start = start < 0 ? 0 : (start > a.num - a.B ? a.num - a.B : start);   // (never past the series, whatever the words hold)
+    }
+    fv = fv < 0 ? 0 : (fv > a.B ? a.B : fv);
+    const float* y = a.target + start * a.tstride;
+    const long n = (long)a.B * a.N;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (long e = fv * a.N + (long)blockIdx.x * kEvalThreads + tid; e < n; e += (long)gridDim.x * kEvalThreads) {
+        const int node = (int)(e % a.N);
+        const float p = a.pred[e], t = y[e];
+        const float sc = a.scale ? a.scale[node] : 1.0f, mu = a.mean ? a.mean[node] : 0.0f;
+        const float dz = p - t, d = (t - p) * sc;
+        s0 += (double)(dz * dz);
+        s1 += (double)fabsf(d);
+        s2 += (double)(d * d);
+        s3 += (double)(t * sc + mu);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        s0 += shfl_xor_f64(s0, m);
+        s1 += shfl_xor_f64(s1, m);
+        s2 += shfl_xor_f64(s2, m);
+        s3 += shfl_xor_f64(s3, m);
+    }
+    if (lane == 0) {
+        red[wave * 4 + 0] = s0;
+        red[wave * 4 + 1] = s1;
+        red[wave * 4 + 2] = s2;
+        red[wave * 4 + 3] = s3;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    double t = 0.0;   // lanes 0..3 of wave 0 own one sum each
+    if (lane < 4)
+        for (int w = 0; w < kEvalThreads / 64; ++w) t += red[w * 4 + lane];
+    if (gridDim.x == 1) {
+        if (lane < 4) a.state[lane] += t;
+        if (lane == 0) eval_finish(a, fv, k);
+        return;
+    }
+    if (lane < 4) a.state[kEvalHdr + 4 * blockIdx.x + lane] = t;
+    unsigned* const ticket = reinterpret_cast<unsigned*>(a.state + 6);
+    chain_drain_stores();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    chain_drain_stores();   // (fence first, its own wait kept, then the ticket)
+    unsigned drawn = 0u;
+    if (lane == 0) drawn = chain_add(ticket, 1u);
+    drawn = __shfl(drawn, 0);
+    if (drawn != gridDim.x - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    chain_drain_stores();
+    if (lane < 4) {
+        double tot = 0.0;
+        for (unsigned g = 0; g < gridDim.x; ++g) tot += a.state[kEvalHdr + 4 * g + lane];
+        a.state[lane] += tot;
+    }
+    if (lane == 0) {
+        eval_finish(a, fv, k);
+        chain_st(ticket, 0u);
+    }
+}
+
+// a new pass: the sums, the count, the ticket word and the position words start from zero
+__global__ __launch_bounds__(64) void eval_arm_kernel(double* state, long* pos) {
+    if (threadIdx.x < kEvalHdr) state[threadIdx.x] = 0.0;
+    if (pos && threadIdx.x < 4) pos[threadIdx.x] = 0;
+}
+
 }  // namespace stgcn

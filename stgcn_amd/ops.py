@@ -283,6 +283,60 @@ def mse_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, grad_scale: floa
     return loss, dpred
 
 
+EVAL_STATE_WORDS, EVAL_POS_WORDS = _lib.EVAL_STATE_WORDS, _lib.EVAL_POS_WORDS
+
+
+def eval_state(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A zeroed metric state (float64, ``stgcn_eval_accumulate``'s layout) and zeroed position words (int64) on ``device``."""
+    return (torch.zeros(EVAL_STATE_WORDS, dtype=torch.float64, device=device), torch.zeros(EVAL_POS_WORDS, dtype=torch.int64, device=device))
+
+
+def eval_arm(state: torch.Tensor, pos: Optional[torch.Tensor] = None) -> None:
+    """Start a new evaluation pass: sums, count, ticket word and position words back to zero (``stgcn_eval_arm``, one launch)."""
+    L = _lib.lib()
+    _check_eval_state(L, state, pos)
+    L.check(L.dll.stgcn_eval_arm(state.data_ptr(), _optr(pos), _stream_of(state)), "stgcn_eval_arm")
+
+
+def _check_eval_state(L, state: torch.Tensor, pos: Optional[torch.Tensor]) -> None:
+    if state.dtype != torch.float64 or state.numel() < EVAL_STATE_WORDS or not state.is_contiguous():
+        raise ValueError(f"evaluation state: {EVAL_STATE_WORDS} contiguous float64 words expected, got {state.numel()} x {state.dtype}")
+    if pos is not None and (pos.dtype != torch.int64 or pos.numel() < EVAL_POS_WORDS or not pos.is_contiguous() or pos.device != state.device):
+        raise ValueError(f"evaluation position: {EVAL_POS_WORDS} contiguous int64 words on the state's device expected")
+    if L.is_emulator == state.is_cuda:
+        raise RuntimeError(f"evaluation state is on {state.device}, the bound library is {L.backend}")
+
+
+def eval_accumulate(pred: torch.Tensor, target: torch.Tensor, state: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                    mean: Optional[torch.Tensor] = None, first_valid: int = 0, pos: Optional[torch.Tensor] = None, num_windows: int = 0,
+                    target_stride: Optional[int] = None) -> None:
+    """One minibatch of script/utility.py:90-121 added into ``state`` on the device (``stgcn_eval_accumulate``, one launch, nothing
+    synchronises): ``pred`` (B, N) float32 predictions, ``target`` the (B, N) label rows (with ``pos`` the rows of window 0: the
+    launch reads them ``pos[0] * target_stride`` floats further on and moves ``pos`` on to the next batch), ``scale`` / ``mean`` the
+    per-node inverse z-score or None.  Windows below ``first_valid`` are not counted."""
+    L = _lib.lib()
+    p = pred.detach()
+    _check_device(p, "pred")
+    _check_eval_state(L, state, pos)
+    if p.dim() != 2 or not p.is_contiguous() or target.dtype != torch.float32 or not target.is_contiguous() or target.shape != p.shape:
+        raise ValueError(f"eval_accumulate: contiguous float32 (B, N) tensors expected, got {tuple(p.shape)} / {tuple(target.shape)}")
+    B, N = p.shape
+    for t, what in ((scale, "scale"), (mean, "mean")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != N or not t.is_contiguous() or t.device != p.device):
+            raise ValueError(f"eval_accumulate: {what} must be {N} contiguous float32 values on {p.device}")
+    L.check(L.dll.stgcn_eval_accumulate(p.data_ptr(), target.data_ptr(), B, N, _optr(scale), _optr(mean), int(first_valid), _optr(pos),
+                                        N if target_stride is None else int(target_stride), int(num_windows), state.data_ptr(),
+                                        _stream_of(p)), "stgcn_eval_accumulate")
+
+
+def eval_metrics(words) -> dict:
+    """The reference's numbers from the first five words of a metric state (host values): MSE in z-scored units
+    (utility.py:90-101), MAE / RMSE / WMAPE after the inverse transform (:111-121), and the element count."""
+    import math
+    sse, sad, ssd, sy, n = (float(w) for w in words[:5])
+    return {"mse": sse / n, "mae": sad / n, "rmse": math.sqrt(ssd / n), "wmape": sad / sy, "elements": int(n)}
+
+
 class _PendingLoss:
     """MSE loss waiting to be formed inside the head's backward (``stgcn_outblock_backward_loss``): ``mse_backward`` posts it, the
     ``_OutBlockFn.backward`` that receives the placeholder gradient takes it."""

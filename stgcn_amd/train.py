@@ -640,3 +640,170 @@ class GraphedTrainStep:
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM)
             self.g2.replay()
         return self.loss
+
+
+def _workspace_owners(model):
+    from .layers import OutputBlock, STConvBlock
+    return [(name or type(m).__name__, m) for name, m in model.named_modules() if isinstance(m, (STConvBlock, OutputBlock))]
+
+
+class GraphedEvalPass:
+    """The reference's per-epoch scoring (``evaluate_model`` + ``evaluate_metric``, script/utility.py:90-121; main.py:173, :184-203) as
+    hipGraph replays over a split that stays on the device: one batch = the model's eval-mode forward on the strided in-place view of the
+    series + ONE ``stgcn_eval_accumulate`` launch that adds the batch into a device-resident fp64 state and moves the position words on
+    to the next batch.  ``run()`` = arm, ``ceil(num / B)`` replays, one synchronise, one 40-byte copy -- instead of a gather, ~7 launches
+    from Python and a host synchronisation per batch.
+
+    ``series``: the z-scored (rows, N) split (numpy or tensor); ``num = rows - n_his - n_pred`` windows as the reference counts them
+    (script/dataloader.py:36).  ``scaler``: a fitted ``data.ZScore`` (``scale_`` / ``mean_``) for MAE / RMSE / WMAPE in the data's units,
+    None = the identity.  Ragged tail: batch k starts at window ``min(k B, num - B)`` and counts only the windows from ``k B`` on, so
+    the last batch overlaps its predecessor instead of reading past the series, with ONE graph (LayerNorm is per (b, t) slab: a
+    window's prediction does not depend on the batch that carries it).  ``num < B`` raises ValueError (``data.evaluate_*`` serve such splits).
+    ``capture=False`` runs the identical launches eagerly (CPU emulator; also the fallback when capture raises).
+
+    Beside a live ``GraphedTrainStep`` on the same model, in either construction order: the pass touches neither the dropout counter nor the
+    optimizer's step counter nor ``model._step_counters`` (an eval-mode forward hands no counters to the pack launch), and its position
+    words are its own.  A captured graph holds the addresses of the model's workspaces, which ``ops.WorkspaceCache`` reallocates when a
+    plan grows: the constructor refuses (RuntimeError, before anything moved) if its forward would grow an existing workspace, and holds
+    on to the buffers its own graph uses.  ``close()`` / the context manager drop the index bindings."""
+
+    def __init__(self, model, series, n_his: int, n_pred: int, batch_size: int, scaler=None, capture: bool = True):
+        import numpy as np
+        from . import _lib, ops
+        self.model, self.B, self.n_his, self.n_pred = model, int(batch_size), int(n_his), int(n_pred)
+        emu = _lib.lib().is_emulator
+        dev = next(model.parameters()).device
+        if not torch.is_tensor(series):
+            series = torch.as_tensor(np.asarray(series, dtype=np.float32))
+        self.series = series.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if self.series.dim() != 2:
+            raise ValueError(f"GraphedEvalPass: series must be (rows, N), got {tuple(self.series.shape)}")
+        rows, N = self.series.shape
+        B = self.B
+        self.num = int(rows) - self.n_his - self.n_pred
+        if B < 1 or self.num < B:
+            raise ValueError(f"GraphedEvalPass: the split has {self.num} windows, fewer than one batch of {B} "
+                             f"(use data.evaluate_model / data.evaluate_metric for it)")
+        self.batches = (self.num + B - 1) // B
+        cd = getattr(model, "compute_dtype", None)
+        # a model with bf16 activations reads its windows from a bf16 copy of the series (made once; labels and metrics stay fp32)
+        self.series_x = self.series if cd in (None, self.series.dtype) else self.series.to(cd)
+        self.x = torch.as_strided(self.series_x, (B, 1, self.n_his, N), (N, self.n_his * N, N, 1))     # window b = rows [b, b + n_his)
+        self.y = self.series[self.n_his + self.n_pred - 1:self.n_his + self.n_pred - 1 + B]            # label rows of windows 0 .. B-1
+        self.state, self.pos = ops.eval_state(dev)
+        self.scale = self.mean = None
+        if scaler is not None:
+            self.scale = torch.as_tensor(np.asarray(scaler.scale_, dtype=np.float32).reshape(-1)).to(dev).contiguous()
+            self.mean = torch.as_tensor(np.asarray(scaler.mean_, dtype=np.float32).reshape(-1)).to(dev).contiguous()
+            if self.scale.numel() != N or self.mean.numel() != N:
+                raise ValueError(f"GraphedEvalPass: the scaler describes {self.scale.numel()} columns, the series has {N}")
+        self._refuse_workspace_growth(ops, B, cd or torch.float32)
+        before = {name: {c: b.data_ptr() for c, b in m._ws.bufs.items()} for name, m in _workspace_owners(model)}
+        self.index = self.pos[0:1]                   # first window of the batch: the forward's input and the labels move with it
+        ops.bind_input_index(self.x, self.index, N)
+        self.graph = None
+        was_training = model.training
+        model.eval()
+        try:
+            use_graph = bool(capture) and not emu and self.series.is_cuda
+            ops.eval_arm(self.state, self.pos)
+            if use_graph:
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    self._batch()                    # warm-up: allocator state, workspaces, operator caches
+                    self._batch()
+                torch.cuda.current_stream(dev).wait_stream(side)
+                torch.cuda.synchronize(dev)
+            else:
+                self._batch()
+            moved = [f"{name} (chain {c})" for name, m in _workspace_owners(model) for c, p in before[name].items()
+                     if m._ws.bufs[c].data_ptr() != p]
+            if moved:
+                raise RuntimeError(f"GraphedEvalPass: the workspace of {', '.join(moved)} was reallocated by the evaluation forward at batch size "
+                                   f"{B}; a captured training step still holds the old address.  Build the evaluation pass before the "
+                                   f"training step, or use a batch size no larger than the training step's")
+            # the buffers this pass's graph reads and writes stay alive with it, whatever a later, larger plan does to the caches
+            self._ws_keep = [b for _, m in _workspace_owners(model) for b in m._ws.bufs.values()]
+            if use_graph:
+                try:
+                    g = torch.cuda.CUDAGraph()
+                    cap = dict(capture_error_mode="thread_local") if (dist.is_available() and dist.is_initialized()) else {}
+                    with torch.cuda.graph(g, **cap):
+                        self._batch()
+                    ops.eval_arm(self.state, self.pos)
+                    g.replay()                       # a capture / replay problem surfaces here, not inside an epoch
+                    torch.cuda.synchronize(dev)
+                    self.graph = g
+                except Exception as e:  # noqa: BLE001 -- the same launches run eagerly instead
+                    import warnings
+                    warnings.warn(f"GraphedEvalPass: hipGraph capture failed ({e!r}); running the batches eagerly")
+                    torch.cuda.synchronize(dev)
+                    self.graph = None
+        except BaseException:
+            ops.unbind_input_index(self.x)
+            raise
+        finally:
+            model.train(was_training)
+
+    def _refuse_workspace_growth(self, ops, B, dtype):
+        """Raise before anything is reallocated if this pass's forward needs more workspace than a module already owns."""
+        from .layers import STConvBlock
+        T = self.n_his
+        for name, m in _workspace_owners(self.model):
+            if isinstance(m, STConvBlock):
+                need = max(ops.query_plan(ops.make_desc(m.cfg, B, T, tr, tr, dtype=dtype)).ws_floats for tr in (True, False))
+                T -= 2 * (m.cfg.Kt - 1)
+            elif ops.head_supported(m.cfg):
+                need = max(ops.query_head_plan(ops.make_head_desc(m.cfg, B, T, tr, tr, dtype=dtype)).ws_floats for tr in (True, False))
+            else:
+                continue
+            have = m._ws.bufs.get(0)
+            if have is not None and have.numel() < need:
+                raise RuntimeError(f"GraphedEvalPass: the evaluation forward at batch size {B} needs {need} workspace floats in {name}, which "
+                                   f"owns {have.numel()}: its workspace would grow and move under a captured training step.  Build the "
+                                   f"evaluation pass before the training step, or use a batch size no larger than the training step's")
+
+    def _batch(self):
+        from . import ops
+        with torch.no_grad():
+            pred = self.model(self.x).reshape(self.B, -1)
+            if pred.dtype != torch.float32 or not pred.is_contiguous():
+                pred = pred.float().contiguous()
+            ops.eval_accumulate(pred, self.y, self.state, self.scale, self.mean, pos=self.pos, num_windows=self.num)
+
+    def run(self) -> dict:
+        """One pass over the split: {"mse", "mae", "rmse", "wmape"} as the reference defines them (floats) and "windows" (int)."""
+        from . import ops
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            ops.eval_arm(self.state, self.pos)
+            if self.graph is not None:
+                for _ in range(self.batches):
+                    self.graph.replay()
+            else:
+                for _ in range(self.batches):
+                    self._batch()
+            words = self.state[:5].cpu()             # the pass's one synchronisation and one device-to-host copy
+        finally:
+            model.train(was_training)
+        check_in_launch_waits(model)                 # (where the numbers are read)
+        m = ops.eval_metrics(words.tolist())
+        n = m.pop("elements")
+        m["windows"] = n // self.series.shape[1]
+        return m
+
+    def close(self):
+        """Drop the input-index binding of the pass's window view (its graph must not be replayed afterwards)."""
+        from . import ops
+        ops.unbind_input_index(self.x)
+        self.graph = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

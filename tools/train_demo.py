@@ -7,7 +7,9 @@ with StepLR(10, 0.95) per epoch (main.py:147-156), unshuffled minibatches of 32 
 (script/utility.py:90-101), test MAE / RMSE / WMAPE at the end (script/utility.py:103-121).
 
 The training loop is `GraphedTrainStep(series=...)`: the z-scored (time, N) training series stays resident on the GPU and the
-captured step windows it in place.  One JSON line per epoch and one for the test metrics; a persistence forecast
+captured step windows it in place.  Validation and test scoring are `GraphedEvalPass`es (built once, before the training step, and
+replayed every epoch): the metrics are summed on the device, `eval_s` beside `epoch_s` is the wall time of the validation pass.
+One JSON line per epoch and one for the test metrics; a persistence forecast
 (y_hat = last observed value) on the same windows is printed beside them for scale.
 
   python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion]
@@ -45,7 +47,7 @@ def main():
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
-    from stgcn_amd.train import GraphedTrainStep, make_optimizer
+    from stgcn_amd.train import GraphedEvalPass, GraphedTrainStep, make_optimizer
 
     assert torch.cuda.is_available(), "needs the MI355X (no CPU fallback)"
     dev = torch.device("cuda", 0)
@@ -68,13 +70,14 @@ def main():
     series = torch.from_numpy(train.astype(np.float32)).to(dev)
     x0 = torch.zeros(BS, 1, N_HIS, n, device=dev)
     y0 = torch.zeros(BS, n, device=dev)
+    # the evaluation passes first: their graphs keep the workspaces they captured, and the training step's constructor may still grow them
+    val_pass = GraphedEvalPass(model, val, N_HIS, a.n_pred, BS)
+    test_pass = GraphedEvalPass(model, test, N_HIS, a.n_pred, BS, scaler=zs)
     model.train()
     step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred)
     windows = series.shape[0] - N_HIS - a.n_pred + 1
     steps_per_epoch = windows // BS
-    val_s = data.WindowSampler(val, N_HIS, a.n_pred, dev)
     test_s = data.WindowSampler(test, N_HIS, a.n_pred, dev)
-    mse = torch.nn.MSELoss()
 
     for epoch in range(a.epochs):
         model.train()
@@ -88,12 +91,15 @@ def main():
         step.check()                            # (once per epoch, where the loss is read: names the operator if an in-launch wait gave up)
         sched.step()
         opt.sync_lr()                           # the captured AdamW reads its learning rate from device memory
-        val_loss = data.evaluate_model(model, mse, val_s.batches(BS))
+        t0 = time.perf_counter()
+        val_loss = val_pass.run()["mse"]        # one synchronise per pass (script/utility.py:90-101 on the device)
+        eval_s = time.perf_counter() - t0
         print(json.dumps({"epoch": epoch + 1, "train_loss": round(float(acc.item()) / steps_per_epoch, 6), "val_loss": round(val_loss, 6),
-                          "lr": opt.param_groups[0]["lr"], "steps": steps_per_epoch, "epoch_s": round(el, 3),
+                          "lr": opt.param_groups[0]["lr"], "steps": steps_per_epoch, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
                           "train_windows_per_s": round(steps_per_epoch * BS / el, 1)}), flush=True)
 
-    mae, rmse, wmape = data.evaluate_metric(model, test_s.batches(BS), zs)
+    m = test_pass.run()
+    mae, rmse, wmape = m["mae"], m["rmse"], m["wmape"]
     # persistence forecast on the same test windows, in the original units
     ys, ps = [], []
     for x, y in test_s.batches(BS):
