@@ -21,12 +21,6 @@ namespace {
 thread_local char g_err[512] = "";
 // storage / arithmetic type of the activations of the call being served (set by every entry point from its descriptor)
 thread_local bool g_bf16 = false;
-// Default OFF: measured on MI355X (profiles/r4-02_chain_ab.txt) the chained forward of C2's second block is SLOWER than three launches
-// (tmp_conv1 + graph conv: 67.4 us against 28.6 + 14.7; all three stages: 75.7 against 61.7): a launch has ONE register and LDS budget, the
-// widest role's (tc1_fwd: 133 VGPRs, 3 waves per SIMD), and a workgroup is only dispatched when the whole block -- surplus waves included --
-// fits, so a graph-conv workgroup (73 VGPRs, ~5 per CU on its own) cannot start beside a tmp_conv1 workgroup at all and runs one per CU
-// afterwards.  The protocol itself is sound (0 wrong words in 600 launches of tools/ubench/chain_probe.hip, all GPU tests green with it).
-constexpr int kChainDefault = 0;   // (see fwd_chain_mode)
 std::atomic<long long> g_chain_spin_ticks{kChainSpinTicks};   // bound of one in-launch wait (stgcn_set_chain_spin_ticks; read at launch time by any thread)
 int g_gemm_big_nt = 0;   // stgcn_set_gemm_big_nt: forced column extent of the big bf16 operator GEMM's tiles (0 = heuristic)
 
@@ -140,68 +134,6 @@ inline void launch_log(const char* label, const char* kernel, dim3 grid, dim3 bl
         if (g_bf16) return fail(STGCN_ERR_UNSUPPORTED, "%s: no bf16 variant (bf16 blocks need the fused time-stepping kernels)", what); \
     } while (0)
 
-// ---- side stream ----------------------------------------------------------------------------------------------------
-// The weight-gradient kernels of a backward call depend only on dZ, not on the data-gradient chain that follows it, and
-// both are latency-bound launches of ~1 workgroup per CU, so they could run beside each other.  side_fork(st) returns a
-// stream that starts after everything enqueued on st so far; side_join(st) makes st wait for it (always called before the
-// entry point returns, so callers and hipGraph capture see one stream).  OFF by default: on MI355X the cross-queue
-// dependencies of the 6 fork/join pairs per step cost more than the overlap returns at the C2 size (0.650 vs 0.577 ms per
-// step under hipGraph replay, profiles/r19_r33_experiments.md); STGCN_SIDE_STREAM=1 enables it for larger problems.
-struct SideStream { hipStream_t s; hipEvent_t fork, join; int state; };   // state: 0 not initialised, 1 on, -1 off
-SideStream g_side = {nullptr, nullptr, nullptr, 0};
-hipStream_t side_fork(hipStream_t st) {
-    if (g_side.state == 0) {
-#ifdef STGCN_EXPERIMENTS   // (round 5: measured slower on this stack -- cross-queue dependencies, r19-r33 / r3-37 -- and out of the product build)
-        const char* e = getenv("STGCN_SIDE_STREAM");
-#else
-        const char* e = nullptr;
-#endif
-        g_side.state = -1;
-        if (e && atoi(e) == 1 && hipStreamCreateWithFlags(&g_side.s, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&g_side.fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&g_side.join, hipEventDisableTiming) == hipSuccess)
-            g_side.state = 1;
-    }
-    if (g_side.state < 0) return st;
-    if (hipEventRecord(g_side.fork, st) != hipSuccess || hipStreamWaitEvent(g_side.s, g_side.fork, 0) != hipSuccess) return st;
-    return g_side.s;
-}
-void side_join(hipStream_t st, hipStream_t sd) {
-    if (sd == st) return;
-    if (hipEventRecord(g_side.join, sd) == hipSuccess) (void)hipStreamWaitEvent(st, g_side.join, 0);
-}
-
-// A second, deferred form for the head's weight-gradient launch in a fused training step (desc.defer_reduce): nothing before the step's
-// stgcn_grad_flush reads its partials, so it may run beside the WHOLE backward of the ST blocks -- one fork / join pair per step
-// instead of six.  defer_fork(st) returns the stream to launch on (st itself when off); the join happens in stgcn_grad_flush (or in the next
-// defer_fork).  STGCN_SIDE_WGRAD=0/1 forces (default: see defer_enabled).
-struct DeferStream { hipStream_t s; hipEvent_t fork, join; int state; int pending; };
-DeferStream g_defer = {nullptr, nullptr, nullptr, 0, 0};
-void defer_join(hipStream_t st) {
-    if (!g_defer.pending) return;
-    g_defer.pending = 0;
-    if (hipEventRecord(g_defer.join, g_defer.s) == hipSuccess) (void)hipStreamWaitEvent(st, g_defer.join, 0);
-}
-hipStream_t defer_fork(hipStream_t st) {
-    if (g_defer.state == 0) {
-#ifdef STGCN_EXPERIMENTS
-        const char* e = getenv("STGCN_SIDE_WGRAD");
-#else
-        const char* e = nullptr;
-#endif
-        g_defer.state = -1;
-        if (e && atoi(e) == 1 && hipStreamCreateWithFlags(&g_defer.s, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&g_defer.fork, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&g_defer.join, hipEventDisableTiming) == hipSuccess)
-            g_defer.state = 1;
-    }
-    if (g_defer.state < 0) return st;
-    defer_join(st);   // (a launch of an earlier step that nobody flushed)
-    if (hipEventRecord(g_defer.fork, st) != hipSuccess || hipStreamWaitEvent(g_defer.s, g_defer.fork, 0) != hipSuccess) return st;
-    g_defer.pending = 1;
-    return g_defer.s;
-}
-
 #define STGCN_CHECK_LAUNCH(name)                                                                  \
     do {                                                                                          \
         hipError_t e_ = hipGetLastError();                                                        \
@@ -237,8 +169,7 @@ int check_desc(const stgcn_stblock_desc* d) {
 
 // workgroups (4 waves) of the forward: two 16-row tiles per wave, at most four workgroups per CU
 inline int thin_fwd_wgs(int64_t rows) {
-    static const int tpw_env = STGCN_EXP_ENV("STGCN_THIN_FWD_TPW") ? atoi(STGCN_EXP_ENV("STGCN_THIN_FWD_TPW")) : 2;   // tiles per wave (sweep knob, experiments build)
-    const int tpw = tpw_env < 1 ? 1 : tpw_env;   // (0 or a non-numeric value used to divide by zero)
+    constexpr int tpw = 2;   // tiles per wave
     const int64_t tiles = (rows + 15) / 16, want = (tiles + 4 * tpw - 1) / (4 * tpw), cap = 4L * device_cus();
     return (int)(want < 1 ? 1 : want < cap ? want : cap);
 }
@@ -381,10 +312,6 @@ inline bool mfma_x6() {
     const char* e = getenv("STGCN_MFMA_X6");
     return !(e && e[0] == '0');
 }
-inline bool pack_fusion_on() {
-    static const int off = STGCN_EXP_ENV("STGCN_PACK_FUSE") ? atoi(STGCN_EXP_ENV("STGCN_PACK_FUSE")) == 0 : 0;   // (A/B knob, experiments build)
-    return !off;
-}
 int flush_pending_pack() {
     if (!g_pending_pack.valid) return STGCN_OK;
     g_pending_pack.valid = false;
@@ -449,18 +376,6 @@ int launch_tconv_fwd_nt(const char* label, const TconvFwdArgs& a, hipStream_t st
     }
     return STGCN_OK;
 }
-#ifdef STGCN_EXPERIMENTS
-// v3 kernels (time-complete tiles: one workgroup = 16 nodes x all time steps of one window, weights of the whole K in registers)
-template <int WAVES, int NT, int KCW>
-int launch_tconv_fwd3(const char* label, const TconvFwdArgs& a, hipStream_t st) {
-    constexpr int MG = 2;
-    const int node_tiles = (a.ts.N + 15) / 16;
-    const long B = a.ts.rows / ((long)a.ts.Tdst * a.ts.N);
-    const size_t lds = tconv3_lds_bytes(a.ts.Tsrc, a.ts.C, 16 * WAVES * NT, MG);
-    STGCN_LAUNCH(label, st, (tconv_fwd3_kernel<WAVES, NT, KCW, MG>), dim3((unsigned)(B * node_tiles)), dim3(WAVES * 64), lds, a, node_tiles);
-    return STGCN_OK;
-}
-#endif
 // v4: 32-row x 256-column tiles with streamed, double-buffered weight rounds (the output head; see tconv_fwd4_kernel)
 inline bool tconv4_ok(const TconvFwdArgs& a) {
     static const int off = getenv("STGCN_TCONV4") ? atoi(getenv("STGCN_TCONV4")) == 0 : 0;   // A/B knob
@@ -470,11 +385,8 @@ inline bool tconv4_ok(const TconvFwdArgs& a) {
 // Rows of a head tile.  The C2 head has B * N = 6624 rows: 207 tiles of 32 rows leave 49 CUs idle and give every other CU ONE workgroup.
 // Measured (profiles/r3-05_head_tile_ab.txt): 16-row tiles take the two fc kernels from 18.5 / 16.9 to 15.7 / 13.8 us and the conv from
 // 18.6 to 20.4 us (its 256 KB weight stream per workgroup does not shrink with the tile) -- so the fc kernels default to 16 rows, the
-// conv / transposed conv to 32.  STGCN_HEAD_FC_TILE / STGCN_HEAD_TILE = 16 | 32 override.
-inline int head_tile_rows() {
-    static const int t = STGCN_EXP_ENV("STGCN_HEAD_TILE") ? atoi(STGCN_EXP_ENV("STGCN_HEAD_TILE")) : 32;
-    return t == 16 ? 16 : 32;
-}
+// conv / transposed conv to 32 (their 16-row instances stay compiled).  STGCN_HEAD_FC_TILE = 16 | 32 overrides the fc tile.
+inline int head_tile_rows() { return 32; }
 inline int head_fc_tile_rows() {
     const char* e = getenv("STGCN_HEAD_FC_TILE");   // (read per call: the tests switch it)
     return (e && atoi(e) == 32) ? 32 : 16;
@@ -500,16 +412,6 @@ int launch_tconv_fwd(const char* label, const TconvFwdArgs& a, hipStream_t st) {
         aa.f = a;
         return launch_tconv_fwd4<false>(label, aa, st);
     }
-#ifdef STGCN_EXPERIMENTS
-    static const int ver = getenv("STGCN_TCONV_V") ? atoi(getenv("STGCN_TCONV_V")) : 1;   // 1: row tiles (fastest at C2); 3: time-complete tiles (opt-in)
-    if (ver == 3 && (a.ts.C & 15) == 0 && a.KCH * 16 == a.ts.taps * a.ts.C && a.c1 == 16 * (a.Wap ? 1 : a.c1 / 16) &&
-        tconv3_lds_bytes(a.ts.Tsrc, a.ts.C, 2 * a.Cout, 2) <= 64 * 1024) {
-        if (a.Cout == 64 && a.KCH <= 3) return launch_tconv_fwd3<4, 2, 3>(label, a, st);
-        if (a.Cout == 64 && a.KCH <= 12) return launch_tconv_fwd3<4, 2, 12>(label, a, st);
-        if (a.Cout == 128 && a.KCH <= 4) return launch_tconv_fwd3<8, 2, 4>(label, a, st);
-        if (a.Cout == 128 && a.KCH <= 16) return launch_tconv_fwd3<8, 2, 16>(label, a, st);
-    }
-#endif
     return a.Cout == 64 ? launch_tconv_fwd_nt<2>(label, a, st) : launch_tconv_fwd_nt<4>(label, a, st);
 }
 
@@ -604,12 +506,10 @@ int launch_gso_gemm_bf16(const char* label, const float* Mpad, OperandBuf x, flo
     static const int force_bk = getenv("STGCN_GEMM_BF16_BK") ? atoi(getenv("STGCN_GEMM_BF16_BK")) : 0;
     const int bk = force_bk == 32 || force_bk == 64 ? force_bk : kGbDefaultBK;
     const int split = g_gc_precision == 1 && !g_bf16;   // (bf16 activations: operands are bf16 numbers already, one MFMA per product)
-    {   // 256 x (32 * NT) tiles, one workgroup per CU (gso_gemm_bf16_big_kernel); STGCN_GEMM_BIG=0: the 128 x 128 kernel
-        static const int off = STGCN_EXP_ENV("STGCN_GEMM_BIG") ? atoi(STGCN_EXP_ENV("STGCN_GEMM_BIG")) == 0 : 0;
-        static const int env_nt = STGCN_EXP_ENV("STGCN_GEMM_BIG_NT") ? atoi(STGCN_EXP_ENV("STGCN_GEMM_BIG_NT")) : 0;
-        const int force_nt = g_gemm_big_nt ? g_gemm_big_nt : env_nt;   // stgcn_set_gemm_big_nt (tests force every instance) before the environment
+    {   // 256 x (32 * NT) tiles, one workgroup per CU (gso_gemm_bf16_big_kernel); the 128 x 128 kernel otherwise
+        const int force_nt = g_gemm_big_nt;   // stgcn_set_gemm_big_nt (tests force every instance)
         static const int big_bk = getenv("STGCN_GEMM_BIG_BK") && atoi(getenv("STGCN_GEMM_BIG_BK")) == 32 ? 32 : 64;   // r3-17: 64-deep steps 6 % faster
-        if (!off && !split && NP % kGbBigBM == 0) {
+        if (!split && NP % kGbBigBM == 0) {
             const long CP = gc_operand_cols(slabs);
             const int rts = NP / kGbBigBM, cus = device_cus();
             int best = 0;
@@ -734,47 +634,6 @@ int launch_gconv_fwd(GconvFwdArgs a, hipStream_t st) {
     const int HT = a.NP / 16;
     int pf = (HT + 3) / 4, pb = 1;
     gc_parts_override(pf, pb);
-#ifdef STGCN_EXPERIMENTS
-    {   // operator-stationary variant: the wave's operator fragments in registers, several slabs per workgroup
-        static const int per_cu = getenv("STGCN_GC_REG") ? atoi(getenv("STGCN_GC_REG")) : 0;   // opt-in (measured equal / slower at C2 and at bs 128): workgroups per CU
-        const int off = per_cu <= 0;
-        const int nterm = a.Ks - 1, KCH = a.NP / 16;
-        if (!off && (nterm == 1 || nterm == 2) && KCH <= 21 && a.NP * 4 <= 1024) {
-            const int parts = (HT + 3) / 4;
-            a.parts = parts;
-            static int cus = 0;
-            if (!cus) {
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            }
-            // about one workgroup per CU: groups = CUs / parts slab ranges
-            int groups = per_cu * cus / parts;
-            if (groups < 1) groups = 1;
-            if (groups > a.slabs) groups = (int)a.slabs;
-            const int spw = (int)((a.slabs + groups - 1) / groups);
-            groups = (int)((a.slabs + spw - 1) / spw);
-            const size_t lds = (size_t)2 * 16 * (a.NP + 4) * sizeof(float);
-            const dim3 grid((unsigned)(groups * parts)), blk(256);
-            if (KCH <= 13 && nterm == 2) STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_reg_kernel<13, 2>), grid, blk, lds, a, spw);
-            else if (KCH <= 13) STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_reg_kernel<13, 1>), grid, blk, lds, a, spw);
-            else if (nterm == 2) STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_reg_kernel<21, 2>), grid, blk, lds, a, spw);
-            else STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_reg_kernel<21, 1>), grid, blk, lds, a, spw);
-            return STGCN_OK;
-        }
-    }
-#endif
-#ifdef STGCN_EXPERIMENTS
-    {   // persistent operator-stationary form: one workgroup per CU walking >= 2 slabs (gconv_fwd_pers_kernel; measured slower, pass r6-09)
-        static const int pers = getenv("STGCN_GC_PERS") ? atoi(getenv("STGCN_GC_PERS")) : 0;
-        const int nterm = a.Ks - 1;
-        const long sets = device_cus() / 4;
-        if (pers && (nterm == 1 || nterm == 2) && HT <= 16 && !(g_slab_gc_precision > 0 && !g_bf16) && a.slabs >= 2 * sets &&
-            gconv_fwd_pers_lds_bytes(a.NP, a.Ks) <= 160 * 1024) {
-            STGCN_LAUNCH_ET("gconv_fwd", st, (gconv_fwd_pers_kernel<ET>), dim3((unsigned)(4 * sets)), dim3(256), gconv_fwd_pers_lds_bytes(a.NP, a.Ks), a, (int)sets);
-            return STGCN_OK;
-        }
-    }
-#endif
     const GcGeom g = gc_geom(HT, pf);
     a.parts = g.parts;
     const dim3 grid((unsigned)(a.slabs * g.parts)), blk(g.waves * 64);
@@ -786,21 +645,8 @@ int launch_gconv_fwd(GconvFwdArgs a, hipStream_t st) {
         return STGCN_OK;
     }
     const size_t lds = (size_t)16 * (a.NP + 4) * sizeof(float);   // X0 transposed
-    // STGCN_GC_SP=2 (opt-in): two slabs per workgroup, every operator fragment a wave loads feeds both.  Measured equal at C2 and 3 % slower at
-    // C3 (r3-26 / r3-27): the product loop was bound by the latency of its own fragment loads, not by their volume
-#ifdef STGCN_EXPERIMENTS   // (retired from the product build in round 5: a knob that never won)
-    static const int force_sp = getenv("STGCN_GC_SP") ? atoi(getenv("STGCN_GC_SP")) : 0;
-    const bool sp2 = a.Ks > 1 && g.maxq <= 2 && force_sp == 2;
-    if (sp2) {
-        const dim3 grid2((unsigned)(cdiv(a.slabs, 2) * g.parts));
-        if (g.maxq <= 1) STGCN_LAUNCH_ET("gconv_fwd", st, (gconv_fwd_kernel<1, 16, ET, 2>), grid2, blk, 2 * lds, a);
-        else STGCN_LAUNCH_ET("gconv_fwd", st, (gconv_fwd_kernel<2, 8, ET, 2>), grid2, blk, 2 * lds, a);
-        return STGCN_OK;
-    }
-#endif
-    {   // bf16 activations: the operator products from the operator's bf16 fragment plane on 32-deep MFMAs (gconv_fwd_body B16P; STGCN_GC_B16P=0: the 16-deep form)
-        const char* e = STGCN_EXP_ENV("STGCN_GC_B16P");
-        if (g_bf16 && a.Ks > 1 && g.maxq <= 2 && !(e && e[0] == '0')) {
+    {   // bf16 activations: the operator products from the operator's bf16 fragment plane on 32-deep MFMAs (gconv_fwd_body B16P)
+        if (g_bf16 && a.Ks > 1 && g.maxq <= 2) {
             const size_t ldsp = gconv_fwd_b16p_lds_bytes(a.NP, a.N);
             if (g.maxq <= 1) STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_b16p_kernel<1, 16>), grid, blk, ldsp, a);
             else STGCN_LAUNCH("gconv_fwd", st, (gconv_fwd_b16p_kernel<2, 8>), grid, blk, ldsp, a);
@@ -835,17 +681,6 @@ int launch_bwd_data(const char* label, const TconvBwdDataArgs& a, int ntt, hipSt
     return STGCN_OK;
 }
 
-// Chained forward launches (stgcn_device.hip.h): 0 = every stage its own launch, 1 = tmp_conv1 + graph conv in one launch, 2 = the whole
-// forward of a block (tmp_conv1 + graph conv + tmp_conv2 / LayerNorm / dropout) where the shapes allow.  STGCN_CHAIN overrides (A/B runs);
-// the hand-off relies on write-through stores, so a build with STGCN_WT_STORES=0 never chains.
-inline int fwd_chain_mode() {
-#if !STGCN_WT_STORES
-    return 0;
-#else
-    const char* e = getenv("STGCN_CHAIN");
-    return e ? atoi(e) : kChainDefault;
-#endif
-}
 // The head's forward as ONE launch (head_fwd_kernel, stgcn_kernels_fwd.hip.h): default on; STGCN_HEAD_FUSE=0 restores the conv + fc launches
 // (A/B runs), 2 / 4 admit only the 32- / 64-row tile (tests).  The exchange of the row statistics relies on write-through stores.
 inline int head_fuse_mode() {
@@ -868,16 +703,14 @@ int launch_gconv_bwd(GconvBwdArgs a, hipStream_t st) {
     const int HT = a.NP / 16;
     int pf = 0, pb = 1;
     gc_parts_override(pf, pb);
-    {   // round 3: slab split over parts, parameter-gradient jobs on their own waves (gconv_bwd2_kernel); STGCN_GCBWD2=0: the one-workgroup-per-slab kernel
-        static const int off = STGCN_EXP_ENV("STGCN_GCBWD2") ? atoi(STGCN_EXP_ENV("STGCN_GCBWD2")) == 0 : 0;
+    {   // round 3: slab split over parts, parameter-gradient jobs on their own waves (gconv_bwd2_kernel)
         const int force_parts = getenv("STGCN_GCBWD2_PARTS") ? atoi(getenv("STGCN_GCBWD2_PARTS")) : 0;   // (read per call: the tests force geometries)
         // One node tile per tile wave (<= 8 tile waves per workgroup), and the whole grid resident in ONE round: every part re-stages the
         // slab's dY and re-forms all G_k, so a grid of SEVERAL parts that needs more rounds than the slab kernel costs more than it returns
         // (measured at the C3 size, 640 slabs x 3 parts on 512 slots: 120 us against 76 us; at C2, 320 x 2 on 768 slots: 27.2 against 30.0 us).
-        const char* eb = STGCN_EXP_ENV("STGCN_GC_B16P");
-        const bool b16p = g_bf16 && a.Ks > 1 && !(eb && eb[0] == '0');   // bf16 activations: G_k as bf16 planes, products from the operator's bf16 plane (32-deep MFMAs)
+        const bool b16p = g_bf16 && a.Ks > 1;   // bf16 activations: G_k as bf16 planes, products from the operator's bf16 plane (32-deep MFMAs)
         const size_t lds2 = gconv_bwd2_lds_bytes(a.NP, a.N, a.Ks, b16p);   // (G_k tiles + dY rows + the job waves' transposition tiles)
-        if (!off && lds2 <= 150 * 1024 && HT <= 64) {
+        if (lds2 <= 150 * 1024 && HT <= 64) {
             int best = 0;
             for (int parts = (HT + 7) / 8; parts <= HT && !force_parts; ++parts) {
                 const int per = (HT + parts - 1) / parts, njw = gcbwd2_job_waves(a.Ks, parts, per > 8 ? 8 : per);
@@ -946,8 +779,7 @@ int launch_bwd_weight(const char* label, const TconvBwdWeightArgs& a, const Wgra
 
 // two independent weight gradients (the head's conv and fc1) in ONE launch when both take the <4 m-tiles> variants
 inline bool wgrad_pair_ok(const TconvBwdWeightArgs& a1, const WgradGeom& w1, const TconvBwdWeightArgs& a2, const WgradGeom& w2) {
-    static const int off = STGCN_EXP_ENV("STGCN_WGRAD_PAIR") ? atoi(STGCN_EXP_ENV("STGCN_WGRAD_PAIR")) == 0 : 0;   // A/B knob
-    return !off && a1.NC == 256 && w1.MTW == 4 && a2.NC == 128 && w2.MTW == 4 && (a1.ts.C & 3) == 0 && (a2.ts.C & 3) == 0;
+    return a1.NC == 256 && w1.MTW == 4 && a2.NC == 128 && w2.MTW == 4 && (a1.ts.C & 3) == 0 && (a2.ts.C & 3) == 0;
 }
 int launch_wgrad_pair(const char* label, const TconvBwdWeightArgs& a1, const WgradGeom& w1, const TconvBwdWeightArgs& a2, const WgradGeom& w2,
                       hipStream_t st) {
@@ -1142,8 +974,9 @@ int stgcn_stblock_plan_query(const stgcn_stblock_desc* d, stgcn_stblock_plan* p)
     o = 0;
     // control words of the chained launches FIRST: their offset must not depend on need_dx / training, because the pack launch that zeroes
     // them may have been planned with other flags than the forward that uses them (stgcn_prepack packs a whole model with need_dx = 1)
-    // control words of the forward: header, the arrival counters of A[slab] and G[slab] (chained launches, experiments), then the exchange
-    // words of tmp_conv2 + LayerNorm when several workgroups share a slab (64-bit, up to kTc2LnMaxPeers per slab)
+    // control words of the forward: header, 2 * slabs1 words that no kernel reads any more (the arrival counters of the removed chained
+    // forward; kept so that ws_floats and every ws_* offset stay where they were -- shrinking the workspace is a separate change), then the
+    // exchange words of tmp_conv2 + LayerNorm when several workgroups share a slab (64-bit, up to kTc2LnMaxPeers per slab)
     p->chain_words = kChainHdr + 2 * v.slabs1 + 2 * kTc2LnMaxPeers * v.slabs2;
     p->ws_chain = take(p->chain_words);
     p->ws_W1p = take((int64_t)v.NC1 * v.KP1);
@@ -1343,75 +1176,12 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
     // a parked model-level pack (stgcn_prepack): fused with this block's thin first layer when that is what comes next, else launched now
     const bool thin_first = pl.thin_tc1 && thin_wave_tiles() &&
                             !(!pl.recompute_tc1 && !d->x_bstride && !d->x_index_dev && tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt));
-    const bool fuse_pack = g_pending_pack.valid && d->prepacked && thin_first && g_pending_pack.st == st && pack_fusion_on() &&
+    const bool fuse_pack = g_pending_pack.valid && d->prepacked && thin_first && g_pending_pack.st == st &&
                            d->c0 == 64 && d->c1 == 16 && d->c_in < d->c0;
     if (!fuse_pack) STGCN_FLUSH_PENDING_PACK();
     rc = d->prepacked ? STGCN_OK : launch_pack(d, P, pl, ws, st);
     if (rc) return rc;
 
-#ifdef STGCN_EXPERIMENTS   // (round 5: the chained launch of round 4 -- measured slower, DESIGN.md section 3c -- left the product build)
-    // ---- chained forward: tmp_conv1 + Align -> graph conv [-> tmp_conv2 + LayerNorm + dropout] as roles of ONE launch -----------------
-    {
-        const int mode = fwd_chain_mode();
-        const int HT = v.NP / 16;
-        const bool tc1_ts = !pl.recompute_tc1 && !d->x_bstride && !d->x_index_dev && tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt);
-        const bool slab_gc = !gc_is_tiled(d->N, v.terms) && !(g_slab_gc_precision > 0 && !g_bf16);
-        const bool tc2_one = tc2_ln_fwd_fused_ok(d->c1, d->c2, d->Kt, d->N) && d->N <= 256 && v.slabs2 <= 2L * device_cus();
-        if (mode > 0 && tc1_ts && slab_gc && d->c_in == 64 && d->c0 == 64 && d->Kt == 3 && d->act == STGCN_ACT_GLU && HT <= 64) {
-            const bool with_tc2 = mode >= 2 && tc2_one && HT <= 16;
-            Tc1FwdArgs f1;
-            memset(&f1, 0, sizeof(f1));
-            f1.x = x; f1.Wp = ws + pl.ws_W1p; f1.bias = ws + pl.ws_b1; f1.WaD = ws + pl.ws_WaDense; f1.ba = ws + pl.ws_ba;
-            f1.U = saved + pl.sv_U1; f1.S = saved + pl.sv_S1; f1.A = saved + pl.sv_A;
-            f1.B = d->B; f1.T = d->T; f1.T1 = v.T1; f1.N = d->N; f1.node_tiles = (d->N + 15) / 16;
-            f1.chain_out = 0;                                   // counters [0, slabs1): node tiles of A[slab]
-            GconvFwdArgs f2;
-            memset(&f2, 0, sizeof(f2));
-            f2.A = saved + pl.sv_A; f2.Lp = gso_pad; f2.W = P->gc_w; f2.bias = P->gc_b; f2.Xk = saved + pl.sv_Xk; f2.G = saved + pl.sv_G;
-            f2.N = d->N; f2.NP = v.NP; f2.Ks = v.terms; f2.kipf = d->graph_conv == STGCN_GC_KIPF; f2.slabs = v.slabs1;
-            f2.chain_in = 0; f2.chain_expect = (unsigned)f1.node_tiles;
-            f2.chain_out = with_tc2 ? (int)v.slabs1 : -1;       // counters [slabs1, 2 slabs1): parts of G[slab]
-            // graph-conv geometry: with the third role every workgroup reserves tmp_conv2's 1024 threads and ~60 KB (two per CU), so a slab is ONE
-            // workgroup with a wave per node tile; without it the stand-alone split (4-wave parts, ~5 per CU) stays
-            const GcGeom gg = gc_geom(HT, with_tc2 ? 1 : (HT + 3) / 4);
-            if (gg.maxq == 1) {
-                f2.parts = gg.parts;
-                const int gc_threads = gg.waves * 64;
-                Tc2LnFwdArgs f3;
-                memset(&f3, 0, sizeof(f3));
-                f3.G = saved + pl.sv_G; f3.Wp = ws + pl.ws_W2p; f3.bias = ws + pl.ws_b2; f3.gamma = P->ln_w; f3.beta = P->ln_b;
-                f3.U = pl.stored_US2 ? saved + pl.sv_U2 : nullptr; f3.S = pl.stored_US2 ? saved + pl.sv_S2 : nullptr;
-                f3.y = y; f3.mean = saved + pl.sv_mean; f3.rstd = saved + pl.sv_rstd;
-                f3.T1 = v.T1; f3.T2 = v.T2; f3.N = d->N; f3.NPR = (int)rup(d->N, 16); f3.act = d->act; f3.training = d->training && d->droprate > 0.f;
-                f3.eps = d->ln_eps; f3.keep_scale = 1.0f / (1.0f - d->droprate); f3.thresh = drop_thresh(d->droprate);
-                f3.seed = seed; f3.offset = offset; f3.offset_dev = offset_dev;
-                f3.chain_in = (int)v.slabs1; f3.chain_expect = (unsigned)gg.parts;
-                const long items = (long)d->B * f1.node_tiles;
-                static const int force_per_cu = getenv("STGCN_TC1_FWD_PER_CU") ? atoi(getenv("STGCN_TC1_FWD_PER_CU")) : 0;
-                const long want = (long)device_cus() * (force_per_cu > 0 ? force_per_cu : (g_bf16 ? 2 : 1));
-                const int n1 = (int)(items < want ? items : want), n2 = (int)(v.slabs1 * gg.parts), n3 = with_tc2 ? (int)v.slabs2 : 0;
-                size_t lds = tc1_fwd_lds_bytes(d->c_in, d->Kt);
-                const size_t l2 = gconv_fwd_lds_bytes(v.NP, 1, gg.waves, with_tc2), l3 = with_tc2 ? tc2_ln_fwd_lds_bytes(d->Kt, d->N) : 0;
-                lds = lds > l2 ? lds : l2;
-                lds = lds > l3 ? lds : l3;
-                const int slot = (int)(lds / 4);                // the ticket's LDS word sits behind every role's own LDS
-                lds += 16;
-                ChainCtl cc;
-                cc.words = reinterpret_cast<unsigned*>(ws + pl.ws_chain);
-                cc.ncount = with_tc2 ? 2 * (int)v.slabs1 : (int)v.slabs1;
-                cc.total = (unsigned)(n1 + n2 + n3);
-                cc.spin = g_chain_spin_ticks;
-                const dim3 grid(cc.total);
-                if (with_tc2) STGCN_LAUNCH_ET("stblock_fwd", st, (stblock_fwd_chain_kernel<64, 3, 4, true, ET>), grid, dim3(1024), lds, f1, f2, f3, cc, n1, n2, gc_threads, slot);
-                else STGCN_LAUNCH_ET("tc1_gconv_fwd", st, (stblock_fwd_chain_kernel<64, 3, 4, false, ET>), grid, dim3(512), lds, f1, f2, f3, cc, n1, n2, gc_threads, slot);
-                if (with_tc2) return STGCN_OK;
-                goto after_gconv;
-            }
-        }
-    }
-#endif
-
-    {
     // ---- tmp_conv1 + GLU + Align(c0 -> c1) -----------------------------------------------------
     if (!pl.recompute_tc1 && !d->x_bstride && !d->x_index_dev && tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt)) {
         // time-stepping kernel: weights stationary in registers, every input tile read once (stgcn_kernels_tstep.hip.h)
@@ -1422,13 +1192,8 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
         f.B = d->B; f.T = d->T; f.T1 = v.T1; f.N = d->N; f.node_tiles = (d->N + 15) / 16;
         const long items = (long)d->B * f.node_tiles;
         // workgroups per CU: one for fp32 (its steps are bound by the fp32 matrix pipe: a second chain on the CU made it 12 % slower), two for
-        // bf16 activations (8 x cheaper MFMAs leave a latency chain: C3 34.2 -> 27.1 us, r3-31); STGCN_TC1_FWD_PER_CU forces
-#ifdef STGCN_EXPERIMENTS
-        static const int force_per_cu = getenv("STGCN_TC1_FWD_PER_CU") ? atoi(getenv("STGCN_TC1_FWD_PER_CU")) : 0;
-#else
-        constexpr int force_per_cu = 0;   // (round 5: the per-CU count is decided by the activation type; the knob left the product build)
-#endif
-        const int fwd_per_cu = force_per_cu > 0 ? force_per_cu : (g_bf16 ? 2 : 1);
+        // bf16 activations (8 x cheaper MFMAs leave a latency chain: C3 34.2 -> 27.1 us, r3-31)
+        const int fwd_per_cu = g_bf16 ? 2 : 1;
         const long want = (long)device_cus() * fwd_per_cu;                                    // (stgcn_set_tc1_bwd_wgs overrides the CU count in tests)
         const long by_steps = items * (long)v.T1 / tc1_min_steps(), most = items > by_steps ? items : by_steps;   // (small batches: ranges cut inside items)
         const dim3 grid((unsigned)(most < want ? most : want)), blk(512);                     // equal (item, step) ranges, one workgroup per CU
@@ -1491,10 +1256,7 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
     gc.XT = pl.tiled_gc && v.terms > 1 ? ws + pl.ws_XT : nullptr;
     rc = launch_gconv_fwd(gc, st);
     if (rc) return rc;
-    }
-#ifdef STGCN_EXPERIMENTS
-after_gconv:
-#endif
+
     if (tc2_ln_fwd_fused_ok(d->c1, d->c2, d->Kt, d->N)) {
         // ---- tmp_conv2 + GLU + LayerNorm([N, c2]) + dropout: one workgroup per (b, t2) slab ------------------------------------
         Tc2LnFwdArgs f;
@@ -1515,10 +1277,9 @@ after_gconv:
         f.peer_slots = reinterpret_cast<unsigned long long*>(ws + pl.ws_chain + kChainHdr + 2 * v.slabs1);
         const dim3 grid((unsigned)(v.slabs2 * pp));
         // 16 waves (4 tile groups) when the grid leaves room for it: at most ~2 workgroups per CU (measured at C2: 25.8 -> ?? us)
-        static const int hv_force = STGCN_EXP_ENV("STGCN_TC2LN_HV") ? atoi(STGCN_EXP_ENV("STGCN_TC2LN_HV")) : 0;
         // (up to 384 nodes = 6 tiles per wave of a four-group workgroup: C3's 325-node slabs ran on 8 waves, one workgroup per CU, two rounds)
         // (the 6-tile form only for bf16 activations: with fp32 fragments it needs more than the 128 registers of a 16-wave workgroup)
-        const bool wide = d->N <= (g_bf16 ? 384 : 256) && (hv_force ? hv_force == 4 : v.slabs2 <= 2L * device_cus());
+        const bool wide = d->N <= (g_bf16 ? 384 : 256) && v.slabs2 <= 2L * device_cus();
         const bool small = d->N <= 224;   // 7 row tiles per wave of a two-group workgroup
 #define STGCN_TC2LN(KT_)                                                                                  \
         do {                                                                                              \

@@ -43,7 +43,6 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         ln.slabconst = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b + 2 * v.rows2);
         STGCN_LAUNCH("ln_slab_consts", st, ln_slab_consts_kernel, dim3((unsigned)v.slabs2), dim3(kThreads), 64, ln);
     }
-    hipStream_t sd = st;
     if (bg.k1) {
         // ---- LayerNorm + dropout + gate backward, weight gradient and transposed conv of tmp_conv2 in one time-stepping launch ----
         Tc2BwdArgs a;
@@ -81,16 +80,15 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
     STGCN_LAUNCH("ln_gate_bwd", st, (ln_gate_bwd_kernel<float>), dim3(cdiv(ln.n / 4, kThreads), bg.ln_sg), dim3(kThreads),
                  (8 + 2 * bg.ln_spg) * sizeof(float), ln);
 
-    // ---- weight gradient of tmp_conv2 (needs only dZ2): beside the data-gradient chain ------------------------------
-    sd = side_fork(st);
+    // ---- weight gradient of tmp_conv2 (needs only dZ2) ---------------------------------------------------------------
     TconvBwdWeightArgs wa;
     memset(&wa, 0, sizeof(wa));
     wa.ts.src = saved + pl.sv_G; wa.ts.C = d->c1; wa.ts.taps = d->Kt; wa.ts.N = d->N; wa.ts.Tsrc = v.T1; wa.ts.Tdst = v.T2; wa.ts.dir = 1;
     wa.ts.rows = v.rows2;
     wa.dZ = ws + pl.ws_dZ2; wa.part = part + bg.w2.off; wa.NC = v.NC2; wa.Mpad = bg.w2.Mpad; wa.rows_per_chunk = bg.w2.rows_per_chunk;
     wa.chunks = bg.w2.chunks;
-    rc = launch_bwd_weight("tconv_bwd_weight.tc2", wa, bg.w2, sd);
-    if (rc) { side_join(st, sd); return rc; }
+    rc = launch_bwd_weight("tconv_bwd_weight.tc2", wa, bg.w2, st);
+    if (rc) return rc;
 
     // ---- tmp_conv2 backward-data (+ relu mask) : dZ2 -> dYg ---------------------------------------------
     {
@@ -100,7 +98,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         a.ts.rows = v.rows1;
         a.Wp = ws + pl.ws_W2d; a.KCH = d->Kt * v.NC2 / 16; a.Cin = d->c1; a.Gmask = saved + pl.sv_G; a.dX = ws + pl.ws_dYg;
         rc = launch_bwd_data("tconv_bwd_data.tc2", a, v.CP1 / 16, st);
-        if (rc) { side_join(st, sd); return rc; }
+        if (rc) return rc;
     }
     }
 
@@ -114,7 +112,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         a.Gk = pl.tiled_gc ? ws + pl.ws_Gk : nullptr; a.tiles_per_wg = bg.gc_tiles_per_wg; a.wgs = bg.gc_count;
         a.XT = pl.tiled_gc && v.terms > 1 ? ws + pl.ws_XT : nullptr;
         rc = launch_gconv_bwd(a, st);
-        if (rc) { side_join(st, sd); return rc; }
+        if (rc) return rc;
     }
 
     if (bg.k3) {
@@ -191,7 +189,6 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
 
     // ---- weight gradient of tmp_conv1 (needs dZ1; the thin first layer accumulated it inside thin_tc1_bwd_kernel) ----
     if (!bg.thin) {
-        sd = side_fork(st);   // (no-op unless STGCN_SIDE_STREAM=1) the side stream continues after align_gate_bwd
         TconvBwdWeightArgs wa;
         memset(&wa, 0, sizeof(wa));
         wa.ts.taps = d->Kt; wa.ts.N = d->N; wa.ts.dir = 1;
@@ -199,8 +196,8 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         wa.ts.bstride = d->x_bstride; wa.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); wa.ts.idx_stride = d->x_index_stride;
         wa.dZ = ws + pl.ws_dZ1; wa.part = part + bg.w1.off; wa.NC = v.NC1; wa.Mpad = bg.w1.Mpad; wa.rows_per_chunk = bg.w1.rows_per_chunk;
         wa.chunks = bg.w1.chunks;
-        rc = launch_bwd_weight("tconv_bwd_weight.tc1", wa, bg.w1, sd);
-        if (rc) { side_join(st, sd); return rc; }
+        rc = launch_bwd_weight("tconv_bwd_weight.tc1", wa, bg.w1, st);
+        if (rc) return rc;
     }
     // ---- tmp_conv1 backward-data : dZ1 -> dx ---------------------------------------------------------------
     if (d->need_dx) {
@@ -210,7 +207,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         a.ts.rows = v.rows0;
         a.Wp = ws + pl.ws_W1d; a.KCH = d->Kt * v.NC1 / 16; a.Cin = d->c_in; a.Gmask = nullptr; a.dX = dx;
         rc = launch_bwd_data("tconv_bwd_data.tc1", a, v.CP_in / 16, st);
-        if (rc) { side_join(st, sd); return rc; }
+        if (rc) return rc;
         if (dx_hook && dx_hook->rowstat) {   // no epilogue in this kernel: the hooked LayerNorm's row partials from a pass over dx
             LnBwdArgs hl;
             memset(&hl, 0, sizeof(hl));
@@ -223,7 +220,6 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
     }
 
     }
-    side_join(st, sd);
 
     // ---- final reduction into the reference's parameter layouts (deferred to stgcn_grad_flush when asked) ------------
     if (d->defer_reduce) return STGCN_OK;

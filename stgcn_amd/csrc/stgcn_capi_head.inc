@@ -62,13 +62,8 @@ static HeadGeom head_geom(const stgcn_outblock_desc* d) {
     g.off_fc = take((long)g.fc_wgs * (d->c1 + 2));
     // The two weight gradients share ONE launch (wgrad_pair_kernel) of 100-KB-LDS workgroups, one per CU: together they aim at one resident
     // round (conv : fc1 = 5 : 3 by their work per row), not at one round EACH -- 416 workgroups at C2 were two rounds of short workgroups and
-    // 40 % more partial blocks for the final reduction to read (STGCN_WGRAD_SPLIT=256,256 restores that)
-    static int t_conv = 160, t_fc = 96, t_init = 0;
-    if (!t_init) {
-        t_init = 1;
-        const char* e = STGCN_EXP_ENV("STGCN_WGRAD_SPLIT");
-        if (e) sscanf(e, "%d,%d", &t_conv, &t_fc);
-    }
+    // 40 % more partial blocks for the final reduction to read
+    constexpr int t_conv = 160, t_fc = 96;
     // (measured, pass r4-20: C2 pair 25.5 -> 24.5 us and 0.5 us less in the reduction, C3 step - 2 us; at C5's 131 072 rows the longer
     //  workgroups lose, 115 -> 142 us: big heads keep one round each)
     const bool one_round = g.rows <= 32768;
@@ -241,7 +236,7 @@ int prepack_impl(int32_t n_blocks, const stgcn_prepack_block* blocks, const stgc
         L = trial;
     }
     if (L.nj == 0 && L.pa.ncounters == 0) return STGCN_OK;
-    if (park && pack_fusion_on() && L.nj > 0) {   // parked: the next entry point fuses it with the thin first layer or launches it (flush_pending_pack)
+    if (park && L.nj > 0) {   // parked: the next entry point fuses it with the thin first layer or launches it (flush_pending_pack)
         g_pending_pack.valid = true;
         g_pending_pack.L = L;
         g_pending_pack.st = (hipStream_t)stream;
@@ -452,8 +447,7 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         } else if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
         else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
     }
-    // ---- fc1 weight gradient (needs dh1 only): beside the data-gradient chain (side stream) -----------------------------
-    hipStream_t sd = side_fork(st);
+    // ---- fc1 weight gradient (needs dh1 only) ----------------------------------------------------------------------------
     TconvBwdWeightArgs wa;
     memset(&wa, 0, sizeof(wa));
     wa.ts.src = saved + pl.sv_yln; wa.ts.C = d->c0; wa.ts.taps = 1; wa.ts.N = d->N; wa.ts.Tsrc = g.T1; wa.ts.Tdst = g.T1; wa.ts.dir = 1;
@@ -465,10 +459,10 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
     wcv.ts.src = x; wcv.ts.C = d->c_in; wcv.ts.taps = d->Ko; wcv.ts.Tsrc = d->T; wcv.ts.Tdst = g.T1;
     wcv.dZ = ws + pl.ws_dZ; wcv.part = part + g.wc.off; wcv.NC = g.NC; wcv.Mpad = g.wc.Mpad; wcv.rows_per_chunk = g.wc.rows_per_chunk;
     wcv.chunks = g.wc.chunks;
-    const bool pair = sd == st && wgrad_pair_ok(wcv, g.wc, wfc, g.wf);
+    const bool pair = wgrad_pair_ok(wcv, g.wc, wfc, g.wf);
     if (!pair) {
-        rc = launch_bwd_weight("head.fc1_bwd_weight", wfc, g.wf, sd);
-        if (rc) { side_join(st, sd); return rc; }
+        rc = launch_bwd_weight("head.fc1_bwd_weight", wfc, g.wf, st);
+        if (rc) return rc;
     }
     // ---- LayerNorm + gate backward ---------------------------------------------------------------------------------
     LnBwdArgs ln;
@@ -505,7 +499,7 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
             aa.lnb.dbet = g_bf16 ? ln.dbet_part : nullptr;
         }
         rc = launch_tconv_fwd4<true>("head.tconv_bwd_data", aa, st);
-        if (rc) { side_join(st, sd); return rc; }
+        if (rc) return rc;
         if (dx_hook && dx_hook->rowstat && !epi) hook_pending = true;
     } else if (d->need_dx) {
         TconvBwdDataArgs a;
@@ -514,15 +508,12 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         a.ts.rows = g.rows_in;
         a.Wp = ws + pl.ws_Wd; a.KCH = d->Ko * g.NC / 16; a.Cin = d->c_in; a.Gmask = nullptr; a.dX = dx;
         rc = launch_bwd_data("head.tconv_bwd_data", a, g.CPin / 16, st);
-        if (rc) { side_join(st, sd); return rc; }
+        if (rc) return rc;
         if (dx_hook && dx_hook->rowstat) hook_pending = true;
     }
-    // ---- conv weight gradient (needs dZ, which the fused transposed conv above writes): side stream when enabled -----------------
-    if (sd != st) sd = side_fork(st);
-    // (fused step: the pair's partials are first read by stgcn_grad_flush, so the launch may run beside the ST blocks' backward)
-    rc = pair ? launch_wgrad_pair("head.wgrad_pair", wcv, g.wc, wfc, g.wf, d->defer_reduce ? defer_fork(st) : st)
-              : launch_bwd_weight("head.tconv_bwd_weight", wcv, g.wc, sd);
-    if (rc) { side_join(st, sd); return rc; }
+    // ---- conv weight gradient (needs dZ, which the fused transposed conv above writes) --------------------------------------------
+    rc = pair ? launch_wgrad_pair("head.wgrad_pair", wcv, g.wc, wfc, g.wf, st) : launch_bwd_weight("head.tconv_bwd_weight", wcv, g.wc, st);
+    if (rc) return rc;
     if (hook_pending) {   // the kernel that formed dx had no epilogue for it: the hooked LayerNorm's row partials from a pass over dx
         LnBwdArgs hl;
         memset(&hl, 0, sizeof(hl));
@@ -532,7 +523,6 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         hl.keep_scale = o.keep_scale; hl.thresh = o.thresh; hl.seed = o.seed; hl.offset = o.offset; hl.offset_dev = o.offset_dev;
         STGCN_LAUNCH_ET("ln_bwd_rowstats", st, (ln_bwd_rowstats_kernel<ET>), dim3(cdiv(hl.slabs * (hl.n / 4), kThreads)), dim3(kThreads), 0, hl);
     }
-    side_join(st, sd);
     // ---- final reduction (deferred to stgcn_grad_flush when asked) ------------------------------------------------------------
     if (d->defer_reduce) return STGCN_OK;
     ReduceList RL;
@@ -631,7 +621,6 @@ int stgcn_grad_flush(int32_t n_blocks, const stgcn_flush_block* blocks, const st
                      const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count,
                      const stgcn_adamw_hyper* hyper, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
-    defer_join(static_cast<hipStream_t>(stream));   // (the head's weight-gradient launch of this step, if it ran on the side stream)
     if (opt_count < 0 || (opt_count > 0 && (!opt || !hyper))) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush: optimizer table without hyper-parameters");
     ReduceList RL;
     int rc = flush_job_list(RL, "stgcn_grad_flush", n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, true);
@@ -697,7 +686,6 @@ int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, co
         return stgcn_grad_flush(n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, &h, stream);
     }
     STGCN_FLUSH_PENDING_PACK();
-    defer_join(static_cast<hipStream_t>(stream));
     if (opt_count < 1 || !opt) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_optim: empty optimizer table");
     const bool lion = hyper->kind == STGCN_OPT_LION;
     ReduceList RL;

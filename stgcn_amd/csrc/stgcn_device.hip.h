@@ -53,14 +53,6 @@ __device__ int stgcn_phase_kid;
 #define STGCN_ACC2_STORE(kid, i, cond) ((void)0)
 #endif
 
-// Tuning knobs whose A/B runs are over (each lost or tied at least twice, profiles/HISTORY_*): read from the environment only in
-// -DSTGCN_EXPERIMENTS builds; the product build compiles their defaults in (every live knob doubles a tested surface).
-#ifdef STGCN_EXPERIMENTS
-#define STGCN_EXP_ENV(name) getenv(name)
-#else
-#define STGCN_EXP_ENV(name) (static_cast<const char*>(nullptr))
-#endif
-
 namespace stgcn {
 
 constexpr int kThreads = 256;   // 4 waves per workgroup, one per SIMD
@@ -553,9 +545,10 @@ __device__ __forceinline__ void gate_bwd(float dh, float u, float s, int act, fl
 }
 
 // ================================================================================================
-// Chained launches: consecutive, DEPENDENT stages of a block run as roles of ONE launch; a consumer workgroup
-// starts as soon as the slab it needs is complete instead of after the producer kernel's last workgroup, and its prologue (weights,
-// operator fragments) overlaps the producer's tail.  Protocol (MI355X_MICROARCH.md "inter-workgroup visibility", recipe R1):
+// Hand-offs between the workgroups of ONE launch: a consumer workgroup starts as soon as the data it needs is
+// complete instead of after a producer kernel's last workgroup.  In use by the one-launch head, the tmp_conv2 + LayerNorm peers and the
+// pack / thin-layer fusion (the chained forward of a whole block, which this was written for, was measured slower and removed).
+// Protocol (MI355X_MICROARCH.md "inter-workgroup visibility", recipe R1):
 //   * a workgroup's role and item come from an atomic TICKET, not from blockIdx: tickets are handed out in start order and the stages
 //     are numbered producer first, so a workgroup only ever waits for workgroups that are already running -- no assumption about
 //     dispatch order or residency (a consumer that holds a compute unit can never starve the producer it waits for);
@@ -590,38 +583,6 @@ __device__ __forceinline__ void chain_st(unsigned* p, unsigned v) { *p = v; }
 __device__ __forceinline__ unsigned chain_add(unsigned* p, unsigned v) { const unsigned o = *p; *p = o + v; return o; }
 __device__ __forceinline__ void chain_drain_stores() {}
 #endif
-// virtual block index of this workgroup (all threads call; `slot` = one LDS word the launcher reserved behind the roles' own LDS)
-__device__ __forceinline__ int chain_enter(const ChainCtl& c, unsigned* slot) {
-    if (threadIdx.x == 0) *slot = chain_add(c.words, 1u);
-    __syncthreads();
-    return __builtin_amdgcn_readfirstlane((int)*slot);
-}
-// one lane, after the hand-off stores of the whole workgroup are drained and ordered before this call
-__device__ __forceinline__ void chain_publish(const ChainCtl& c, int idx, unsigned n = 1u) { chain_add(c.words + kChainHdr + idx, n); }
-// thread `leader` waits until counter idx has reached `expected` (all threads of the role call: a workgroup barrier follows)
-__device__ __forceinline__ void chain_wait(const ChainCtl& c, int idx, unsigned expected) {
-    if (threadIdx.x == 0) {
-        const unsigned* p = c.words + kChainHdr + idx;
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (chain_ld(p) < expected) {
-            const long long t0 = wall_clock64();
-            while (chain_ld(p) < expected) {
-                __builtin_amdgcn_s_sleep(24);   // ~0.7 us between polls: hundreds of waiting workgroups share the counters' memory channels with the producers' bumps (tools/ubench/chain_probe.hip)
-                if (wall_clock64() - t0 > c.spin) {   // never hang the device: flag it and go on (the results of this launch are void)
-                    chain_st(c.words + 2, 1u + (unsigned)idx);
-                    break;
-                }
-            }
-        }
-#elif !defined(__HIPCC__)
-        if (chain_ld(p) < expected) {   // (emulator: producers ran to completion before this workgroup started -- a short count is a protocol bug)
-            fprintf(stderr, "emu: chained launch: counter %d holds %u, expected %u (missing publish?)\n", idx, chain_ld(p), expected);
-            abort();
-        }
-#endif
-    }
-    __syncthreads();
-}
 // end of a role body (every wave that is still alive calls): the last workgroup of the launch to get here re-arms the control words
 __device__ __forceinline__ void chain_exit(const ChainCtl& c) {
     __syncthreads();   // no wave of this workgroup publishes after the count below
@@ -635,7 +596,7 @@ __device__ __forceinline__ void chain_exit(const ChainCtl& c) {
 }
 // ---- symmetric exchange between the workgroups of ONE launch: every workgroup publishes, then waits for its PEERS (the row statistics of
 // a LayerNorm slab that several row tiles share).  The launcher guarantees that the whole grid is resident at once (grid <= occupancy x
-// compute units, nothing else on the stream), so every peer is running or about to; the wait is bounded like chain_wait.  The emulator
+// compute units, nothing else on the stream), so every peer is running or about to; the wait is bounded (ChainCtl::spin).  The emulator
 // abandons a workgroup whose peers have not run yet and runs it again after the rest of the grid (tests/emu: peer_defer), without
 // repeating its counter bumps.
 __device__ __forceinline__ void chain_publish_peer(const ChainCtl& c, int idx, unsigned n = 1u) {
@@ -647,7 +608,7 @@ __device__ __forceinline__ void chain_publish_peer(const ChainCtl& c, int idx, u
 // TEST setting (stgcn_set_chain_spin_ticks < 0): the launch's first item withholds its arrival, so that its peers' waits -- bounded by
 // |spin| ticks -- run out for certain and the give-up path (sticky word, poisoned results) can be tested on the device and in the emulator
 __device__ __forceinline__ bool chain_withhold(const ChainCtl& c, long item) { return c.spin < 0 && item == 0; }
-// item of this workgroup by start order (as chain_enter; the emulator hands a re-run workgroup the ticket its abandoned run drew)
+// item of this workgroup by start order (all threads call; `slot` = one LDS word the launcher reserved; the emulator hands a re-run workgroup the ticket its abandoned run drew)
 __device__ __forceinline__ int chain_enter_peer(const ChainCtl& c, unsigned* slot) {
     if (threadIdx.x == 0) {
 #if !defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC__)
@@ -734,7 +695,9 @@ __device__ __forceinline__ unsigned long long chain_poll_word(const ChainCtl& c,
 #endif
     return w;
 }
-// one (x, y) pair of a hand-off array, written through / read past this CU's L1 (base wave-uniform, idx = element index)
+// one (x, y) pair of a hand-off array, written through / read past this CU's L1 (sc1 buffer load; `base` must be wave-uniform: kernel
+// arguments and the virtual block index only; idx = element index).  LIMIT: the descriptor's size and the byte offset are
+// 32-bit -- the window [base, base + nelem) must stay below 2 GiB; callers rebase per slab (the head's row partials: N elements).
 __device__ __forceinline__ void st2_wt(float2* p, float2 v) {
 #if STGCN_WT_STORES && defined(__HIP_DEVICE_COMPILE__)
     const u32x2_t r = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)};
@@ -754,28 +717,6 @@ __device__ __forceinline__ float2 ld2_sc1(const float2* base, long nelem, int id
     return base[idx];
 #endif
 }
-// 4 consecutive elements of a hand-off tensor, never from this CU's L1 (sc1 buffer load; `base` must be wave-uniform: kernel arguments and
-// the virtual block index only).  off = element offset from base.  LIMIT: the descriptor's size and the byte offset are 32-bit --
-// the window [base, base + nelem) must stay below 2 GiB; callers rebase per slab (the head's row partials: N elements; the experimental
-// chained forward: one slab / KT slabs), a whole-tensor window on a big B * T * N would clamp silently.
-template <typename ET> __device__ __forceinline__ Raw4<ET> ldraw4_sc1(const ET* base, long nelem, int off) {
-    Raw4<ET> r;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(nelem * (long)sizeof(ET)), 0x00020000);
-    if constexpr (sizeof(ET) == 2) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off * 2, 0, 16);
-        r.v[0] = v[0]; r.v[1] = v[1];
-    } else {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off * 4, 0, 16);
-        r.v = __builtin_bit_cast(f32x4, v);
-    }
-#else
-    (void)nelem;
-    r = ldraw4(base + off);
-#endif
-    return r;
-}
-
 // ---- "bf16x6": fp32-accurate matrix products on the bf16 matrix pipe (round 6) -----------------------------------------------------------
 // An fp32 value splits EXACTLY into three bf16 numbers, x = h + m + l (8 + 8 + 8 significand bits; each residual is exact in fp32).  A product
 // of two such values is 9 terms; the three smallest (m l, l m, l l: below 2^-32 of the product) are dropped, the other six are formed EXACTLY

@@ -63,11 +63,8 @@ inline int tc2_ln_peers(int N, long slabs2) {
     return pp;
 }
 // tc2_bwd_kernel recomputes the gate inputs of tmp_conv2 (and the forward does not store them) for bf16 activations, reads the stored
-// ones for fp32 (see the kernel's header comment for the measurement); STGCN_TC2_RECOMP=0/1 forces one
-inline bool tc2_recompute(int dtype_bf16) {
-    static const int force = STGCN_EXP_ENV("STGCN_TC2_RECOMP") ? atoi(STGCN_EXP_ENV("STGCN_TC2_RECOMP")) : -1;
-    return force >= 0 ? force != 0 : dtype_bf16 != 0;
-}
+// ones for fp32 (see the kernel's header comment for the measurement)
+inline bool tc2_recompute(int dtype_bf16) { return dtype_bf16 != 0; }
 // fewest output steps a range of the two tc1 time-stepping kernels is cut down to when a batch offers fewer (window, node tile) items than
 // the device has compute units (measured at C2 shapes, profiles/r6-08_tc1_small_batch_ranges.txt: bs 4 tc1_bwd 36.0 -> 21.6 us, tc1_fwd
 // 17.6 -> 11.2 us with 2; 1 and 3 are slower -- more partial blocks for the reduction / longer chains)
@@ -94,7 +91,7 @@ inline int g_gc_precision = 0;
 inline int g_slab_gc_precision = 0;
 // matrix products of the BACKWARD kernels of fp32 blocks: 0 exact fp32 MFMAs (default), 1 "bf16x3" (Mma<f32x>: split operands, three bf16
 // MFMAs per product, ~2^-16 relative -- inside the 1e-3 gradient bar, outside "exact fp32"; stgcn_set_bwd_precision)
-inline int g_bwd_precision = (STGCN_EXP_ENV("STGCN_BWD_PRECISION") && !strcmp(STGCN_EXP_ENV("STGCN_BWD_PRECISION"), "bf16x3")) ? 1 : 0;
+inline int g_bwd_precision = 0;
 inline long gc_operand_cols(long slabs) { return (slabs * 16 + 127) / 128 * 128; }   // CP: rows of the bf16 operand form
 // rows ALLOCATED per operand plane: the wide column tiles of gso_gemm_bf16_big_kernel (up to 320 columns) may run past CP
 inline long gc_operand_alloc(long slabs) { return gc_operand_cols(slabs) + 384; }
@@ -197,11 +194,10 @@ inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, i
     // grid-stride workgroups of align_gate_bwd (23.5 KB of LDS each: several per CU for latency hiding).  The thin
     // first-layer kernel carries a 13 KB partial per workgroup, so fewer, longer workgroups win there
     // (measured; 512 = 2 resident workgroups per CU at 62 KB of LDS -- a 513th would wait for a second round).
-    // (round 5: the wave-per-tile thin kernel holds 3 workgroups per CU; STGCN_THIN_WGS overrides the cap for sweeps)
-    static const int thin_cap_env = STGCN_EXP_ENV("STGCN_THIN_WGS") ? atoi(STGCN_EXP_ENV("STGCN_THIN_WGS")) : 0;
+    // (round 5: the wave-per-tile thin kernel holds 3 workgroups per CU)
     // (pass r5-04: 256 / 384 / 512 / 768 workgroups are within noise at C2 and C3; at the 1.3 M rows of the 8192-node graph 768 -- three per
     //  CU, its residency -- take 74 us against 81)
-    const int al_cap = g.thin ? (thin_cap_env > 0 ? thin_cap_env : (rows1 >= (1L << 18) && thin_wave_tiles() ? 768 : 512)) : 1024;   // (768 = three per CU: the wave-per-tile form's residency; the row-tile form of STGCN_THIN=0 holds two)
+    const int al_cap = g.thin ? (rows1 >= (1L << 18) && thin_wave_tiles() ? 768 : 512) : 1024;   // (768 = three per CU: the wave-per-tile form's residency; the row-tile form of STGCN_THIN=0 holds two)
     g.al_wgs = (int)(tiles1 < al_cap ? tiles1 : al_cap);
     long o = 0;
     auto take = [&](long f) { long at = o; o += (f + 63) / 64 * 64; return at; };
@@ -229,12 +225,7 @@ inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, i
     g.k3_wb = 0;
     {   // one workgroup per CU walking an equal-weight range of the (window, node tile, output step) sequence
         const long items = (long)B * g.node_tiles;
-#ifdef STGCN_EXPERIMENTS
-        static const int per_cu = getenv("STGCN_TC1_BWD_PER_CU") ? atoi(getenv("STGCN_TC1_BWD_PER_CU")) : 1;   // (tuning: 2 = two interleaved chains per CU, twice the partials)
-#else
-        constexpr int per_cu = 1;
-#endif
-        long wgs = (long)device_cus() * (per_cu > 0 ? per_cu : 1);
+        long wgs = device_cus();
         // (round 6) small batches: fewer items than compute units -- the ranges are then cut INSIDE items (at least kTc1MinSteps output steps
         // each) instead of leaving one workgroup to walk a whole item alone: the launch is one workgroup's chain, whatever the batch
         const long by_steps = items * (long)T / tc1_min_steps();

@@ -668,192 +668,6 @@ __device__ __forceinline__ void stage_tile_fwd(const TapSrc& ts, long row0, int 
 
 inline int tconv2_lds_floats(int kp, int nc, int rows) { return rows * ((kp > nc ? kp : nc) + 4); }
 
-#ifdef STGCN_EXPERIMENTS   // round-1 experiment variants (never launched by the default build): -DSTGCN_EXPERIMENTS + STGCN_TCONV_V=3
-// ================================================================================================
-// F1 (v3, "time-complete tiles"): one workgroup owns 16 consecutive nodes of one window b for ALL time steps.
-// The input tile X[b, 0..Tsrc-1, n0..n0+15, :] (Tsrc*16 rows of C floats) is read from HBM exactly once into LDS; the
-// Kt taps of the temporal conv are row shifts INSIDE that tile (A operand of output step t, tap k = LDS rows
-// (t + k)*16 .. +16): no im2col copy, no re-reads of neighbouring time steps through L2, identical work per
-// workgroup (row tiles that straddle slabs made v1's workgroups differ 3x in backward).  Every wave keeps the
-// weight fragments of its n-tiles for the WHOLE K in registers (loaded once per workgroup: B * ceil(N/16) = 416
-// workgroups at C2 instead of 1242 tiles re-fetching 96 KB each) and walks the output steps in groups of MG m-tiles;
-// each group's accumulators go through a small LDS tile for the bias / sigmoid / GLU row pass with coalesced 16-byte
-// U, S stores, the LayerNorm row partials and the optional Align(c0 -> c1) GEMM, exactly like v1.
-// Template: WAVES (4 or 8), NT n-tiles per wave (NC = 16 * WAVES * NT), KCW = K/16 chunks held in registers, MG m-tiles
-// per group.  Requires C % 16 == 0 (the 1-channel first layer stays on v1).
-// ================================================================================================
-inline size_t tconv3_lds_bytes(int Tsrc, int C, int NC, int MG) { return ((size_t)Tsrc * 16 * (C + 4) + (size_t)MG * 16 * (NC + 4)) * sizeof(float); }
-
-#ifndef STGCN_V3_STAGGER
-#define STGCN_V3_STAGGER 0
-#endif
-template <int WAVES, int NT, int KCW, int MG>
-__global__ __launch_bounds__(WAVES * 64) void tconv_fwd3_kernel(TconvFwdArgs a, int node_tiles) {
-    constexpr int THREADS = WAVES * 64, NC = 16 * WAVES * NT, COUT = NC / 2, C4N = COUT / 4, LDZ = NC + 4;
-    constexpr int NIT = MG * 16 * C4N / THREADS;   // row-pass iterations per group
-    static_assert(MG * 16 * C4N % THREADS == 0 && THREADS % C4N == 0, "row pass must tile the workgroup");
-    extern __shared__ float stgcn_smem[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
-    const TapSrc& ts = a.ts;
-    const int C = ts.C, ldx = C + 4, Tsrc = ts.Tsrc, Tdst = ts.Tdst, N = ts.N, cpt = C >> 4;   // cpt: K chunks per tap
-    const int item = xcd_item(blockIdx.x, gridDim.x);
-    const int b = item / node_tiles, n0 = (item - b * node_tiles) * 16;
-    float* Xt = stgcn_smem;                       // [Tsrc*16][ldx]
-    float* Zt = Xt + Tsrc * 16 * ldx;             // [MG*16][LDZ]
-    const int KCH = a.KCH;
-    const bool do_align = a.Wap != nullptr;
-
-    STGCN_PHASE(a.Wap ? 1 : 7, 0);
-    // ---- 1. weights of the whole K, bias, align weights -> registers (requested first) ---------------------------
-    f32x4 wb[KCW][NT];
-#pragma unroll
-    for (int q = 0; q < KCW; ++q)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-            wb[q][j] = q < KCH ? ld4(a.Wp + ((size_t)((wave + WAVES * j) * KCH + q) * 64 + lane) * 4) : zero4();
-    const int c4 = tid & (C4N - 1);
-    const f32x4 bp = ld4(a.bias + 4 * c4), bq = ld4(a.bias + COUT + 4 * c4);
-    f32x4 wa[COUT / 16];
-    float bal = 0.f;
-    if (do_align && wave < MG) {
-#pragma unroll
-        for (int kc = 0; kc < COUT / 16; ++kc) wa[kc] = ld4(a.Wap + ((size_t)kc * 64 + lane) * 4);
-        bal = a.ba[l15];
-    }
-
-    STGCN_PHASE(a.Wap ? 1 : 7, 1);
-    // ---- 2. the input tile: all time steps of 16 nodes, once -----------------------------------------------------
-    {
-        const int c4n = C >> 2, c4sh = pow2_shift(c4n), total = Tsrc * 16 * c4n;
-        const float* xb = tap_base(ts) + (size_t)b * tap_bstride(ts) * C;
-        for (int base = 0; base < total; base += THREADS * 8) {
-            f32x4 v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int idx = base + i * THREADS + tid;
-                v[i] = zero4();
-                if (idx < total) {
-                    const int row = fast_div(idx, c4n, c4sh), q4 = idx - row * c4n, t = row >> 4, nn = row & 15;
-                    if (n0 + nn < N) v[i] = ld4(xb + ((size_t)t * N + n0 + nn) * C + 4 * q4);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int idx = base + i * THREADS + tid;
-                if (idx < total) {
-                    const int row = fast_div(idx, c4n, c4sh), q4 = idx - row * c4n;
-                    st4(Xt + row * ldx + 4 * q4, v[i]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    STGCN_PHASE(a.Wap ? 1 : 7, 2);
-#if STGCN_V3_STAGGER > 0
-    // workgroups beyond the first 256 are the second residents of their CU: half a group period behind the first, so that
-    // one workgroup's row pass runs beside the other's MFMAs (experiment knob, units of 2048 cycles)
-    if (blockIdx.x >= 256)
-        for (int i = 0; i < STGCN_V3_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
-
-    // ---- 3. output steps in groups of MG ----------------------------------------------------------------------------
-    for (int mg = 0; mg < Tdst; mg += MG) {
-        f32x4 acc[MG][NT];
-#pragma unroll
-        for (int i = 0; i < MG; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = zero4();
-#pragma unroll
-        for (int q = 0; q < KCW; ++q) {
-            if (q < KCH) {
-                const int tap = q / cpt, kc = q - tap * cpt;
-                f32x4 av[MG];
-#pragma unroll
-                for (int i = 0; i < MG; ++i) {
-                    int t = mg + i;
-                    if (t >= Tdst) t = Tdst - 1;   // padding m-tile of the last group: computed, never stored
-                    av[i] = ld4(Xt + ((t + tap) * 16 + l15) * ldx + kc * 16 + 4 * g);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int i = 0; i < MG; ++i)
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) acc[i][j] = mfma4(av[i][s], wb[q][j][s], acc[i][j]);
-            }
-        }
-        if (mg == 0) STGCN_PHASE(a.Wap ? 1 : 7, 3);
-        if (mg > 0) __syncthreads();   // the previous group's readers of Zt are done
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int col = (wave + WAVES * j) * 16 + l15;
-#pragma unroll
-            for (int i = 0; i < MG; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Zt[(i * 16 + 4 * g + r) * LDZ + col] = acc[i][j][r];
-        }
-        __syncthreads();
-        if (mg == 0) STGCN_PHASE(a.Wap ? 1 : 7, 4);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int row = (tid + it * THREADS) / C4N, t = mg + (row >> 4), nn = row & 15;
-            const bool valid = t < Tdst && n0 + nn < N;
-            const size_t R = ((size_t)b * Tdst + t) * N + n0 + nn;
-            const f32x4 p = ld4(Zt + row * LDZ + 4 * c4), q = ld4(Zt + row * LDZ + COUT + 4 * c4);
-            f32x4 u, sg, h;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                u[i] = p[i] + bp[i];
-                sg[i] = sigmoid_f(q[i] + bq[i]);
-                h[i] = gate_fwd(u[i], sg[i], a.act);
-            }
-            if (valid) {
-                const size_t o = R * COUT + 4 * c4;
-                if (a.U) st4_wt(a.U + o, u);
-                if (a.S) st4_wt(a.S + o, sg);
-                if (a.H) st4_wt(a.H + o, h);
-            }
-            if (a.rowstat) {   // per-row LayerNorm partials: the C4N lanes holding one row are contiguous in the wave
-                float sr = (h[0] + h[1]) + (h[2] + h[3]);
-#pragma unroll
-                for (int m = C4N >> 1; m >= 1; m >>= 1) sr += __shfl_xor(sr, m);
-                const float mr = sr / (float)COUT;
-                float d2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) d2 += (h[i] - mr) * (h[i] - mr);
-#pragma unroll
-                for (int m = C4N >> 1; m >= 1; m >>= 1) d2 += __shfl_xor(d2, m);
-                if (c4 == 0 && valid) a.rowstat[R] = make_float2(mr, d2);
-            }
-            if (do_align) st4(Zt + row * LDZ + 4 * c4, h);   // H tile in place of the P half
-        }
-        if (mg == 0) STGCN_PHASE(a.Wap ? 1 : 7, 5);
-        if (do_align) {
-            __syncthreads();
-            if (wave < MG && mg + wave < Tdst) {   // wave w: A[16 x 16] = H[m-tile w] @ Wa + ba
-                f32x4 c0 = zero4(), c1v = zero4();
-#pragma unroll
-                for (int kc = 0; kc < COUT / 16; ++kc) {
-                    const f32x4 av = ld4(Zt + (wave * 16 + l15) * LDZ + kc * 16 + 4 * g);
-                    c0 = mfma4(av[0], wa[kc][0], c0);
-                    c1v = mfma4(av[1], wa[kc][1], c1v);
-                    c0 = mfma4(av[2], wa[kc][2], c0);
-                    c1v = mfma4(av[3], wa[kc][3], c1v);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int nn = 4 * g + r;
-                    if (n0 + nn < N) a.A[(((size_t)b * Tdst + mg + wave) * N + n0 + nn) * a.c1 + l15] = c0[r] + c1v[r] + bal;
-                }
-            }
-        }
-        if (mg == 0) STGCN_PHASE(a.Wap ? 1 : 7, 6);
-    }
-    STGCN_PHASE(a.Wap ? 1 : 7, 7);
-}
-
-
-#endif  // STGCN_EXPERIMENTS
 
 // ================================================================================================
 // LayerNorm-backward row partials in the epilogue of the kernel that PRODUCES the gradient dy of a LayerNorm output
@@ -987,7 +801,7 @@ struct HeadFcTail {
     uint32_t thresh;
     uint64_t seed, offset;
     const uint64_t* offset_dev;
-    int use_ticket;       // tiles by start order (chain_enter) instead of by blockIdx: grids beyond one resident round
+    int use_ticket;       // tiles by start order (chain_enter_peer) instead of by blockIdx: grids beyond one resident round
 };
 
 template <int TM, int KC, bool PLAIN, typename ET, bool HEADF = false>
@@ -1386,10 +1200,6 @@ __global__ __launch_bounds__(512) void head_fwd_kernel(Tconv4Args aa, HeadFcTail
 // 13 waves for the 207-node graph: measured faster than 8 waves x 2 tiles), 8 waves x MAXQ tiles beyond.
 // ================================================================================================
 struct GconvFwdArgs {
-    // chained launch (ChainCtl of the launch, stgcn_device.hip.h): counter index bases, -1 = not chained on that side
-    int chain_in;        // counter chain_in + slab counts the node tiles of A[slab] that are complete (chain_expect of them)
-    unsigned chain_expect;
-    int chain_out;       // counter chain_out + slab: bumped once per part when this part's rows of G[slab] are written (through)
     const float* A;      // [slabs][N][16]
     const float* Lp;     // fragment-packed T_1 .. T_{Ks-1} (stgcn_gso_prepare), NP*NP floats each
     const float* W;      // cheb: [Ks][16][16] ; kipf: [16][16]
@@ -1402,11 +1212,8 @@ struct GconvFwdArgs {
     float* XT;           // tiled path only: two bf16 operand-form buffers (plan: ws_XT), used when g_gc_precision > 0
 };
 
-// SP = (b, t) slabs per workgroup (2: every operator fragment a wave loads multiplies the X chunks of two slabs; opt-in, STGCN_GC_SP=2:
-// measured equal / slower, the loop was never bound by the volume of that stream).
-inline size_t gconv_fwd_lds_bytes(int NP, int sp, int waves, bool chain_out) {   // X0 transposed (+ one 16 x 20 transposition tile per wave for written-through G rows)
-    return ((size_t)sp * 16 * (NP + 4) + (chain_out ? (size_t)waves * 16 * 20 : 0)) * sizeof(float);
-}
+// SP = (b, t) slabs per workgroup.  Every launch uses SP = 1 (two slabs per workgroup measured equal / slower: the loop was never bound by
+// the volume of the operator stream); the parameter stays because it is part of gconv_fwd_kernel's symbol.
 // B16P (bf16 activations only): the operator products on v_mfma_f32_16x16x32_bf16 from the operator's bf16 fragment PLANE (stgcn_gso_prepare
 // writes it behind the fp32 fragments for stgcn_kernels_gcslab16.hip.h: F[((ht * KC32 + kc) * 64 + lane) * 8 + j] =
 // bf16(T_k[ht*16 + (lane & 15)][kc*32 + 8*(lane >> 4) + j])) and a bf16 copy of X0^T in LDS: half the operator bytes per product, half the
@@ -1417,15 +1224,13 @@ inline size_t gconv_fwd_b16p_lds_bytes(int NP, int N) { return (size_t)16 * (NP 
 __host__ __device__ inline size_t gc_plane_floats(int NP, int N) { return (size_t)(NP / 16) * (gc_np32(N) / 32) * 64 * 4; }   // one plane of one term (gs16_term_floats = two)
 // bid = (slab group, part) index of this workgroup, THREADS = threads of the role (the calling waves: threadIdx.x < THREADS)
 template <int MAXQ, int MAXW, typename ET, int SP, bool B16P = false>
-__device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int bid, const int THREADS, const ChainCtl& chain) {
+__device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int bid, const int THREADS) {
     static_assert(!B16P || (sizeof(ET) == 2 && SP == 1), "the bf16-plane products are the bf16-activation form, one slab per workgroup");
     typedef Mma<ET> MM;
     extern __shared__ float stgcn_smem[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
     const int P = a.parts, part = (int)((unsigned)bid % (unsigned)P);
     const long slab0 = (long)((unsigned)bid / (unsigned)P) * SP;   // slabs slab0 .. slab0 + SP - 1 (the last group may be short)
-    const bool cin = SP == 1 && chain.words && a.chain_in >= 0, cout = SP == 1 && chain.words && a.chain_out >= 0;
-    if (cin) chain_wait(chain, a.chain_in + (int)slab0, a.chain_expect);   // every node tile of A[slab0] has been written (through) by its producer
     // node tile of (wave w, slot q) = part + P * (w + nwaves * q) = wave + WAVES * q with the two names below
     const int wave = part + P * __builtin_amdgcn_readfirstlane(tid >> 6), WAVES = P * (THREADS >> 6);   // (scalar: the tile tests below are branches, not exec masks)
     const int N = a.N, NP = a.NP, LDX = NP + 4, HT = NP >> 4, KCH = NP >> 4;
@@ -1449,7 +1254,7 @@ __device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int 
             for (int u = 0; u < 4; ++u) {
                 const int idx = idx0 + u * THREADS, n = idx >> 2, c4 = idx & 3;
                 const int eo = (n < N ? n : N - 1) * 16 + c4 * 4;
-                rw[u] = cin ? ldraw4_sc1(Asl, (long)N * 16, eo) : ldraw4(Asl + eo);
+                rw[u] = ldraw4(Asl + eo);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1619,29 +1424,6 @@ __device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int 
     }
 
     const float bb = a.bias ? a.bias[l15] : 0.f;
-    if (cout) {
-        // hand-off form: the tile goes through a wave-private LDS tile so that a lane writes 4 channels of one node (16 bytes, write-through);
-        // the storing waves drain, the workgroup meets, ONE lane bumps the slab's counter
-        float* const tw = stgcn_smem + 16 * LDX + (tid >> 6) * (16 * 20);
-#pragma unroll
-        for (int q = 0; q < MAXQ; ++q) {
-            const int ht = wave + WAVES * q;
-            if (ht < HT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) tw[(4 * g + r) * 20 + l15] = fmaxf(yacc[q][0][r] + bb + res[q][0][r], 0.f);
-                wave_lds_sync();
-                const int h = ht * 16 + (lane >> 2);
-                const f32x4 v = ld4(tw + (lane >> 2) * 20 + 4 * (lane & 3));
-                if (h < N) stx4_wt(G_ + ((size_t)slab0 * N + h) * 16 + 4 * (lane & 3), v);
-                wave_lds_sync();
-            }
-        }
-        chain_drain_stores();
-        __syncthreads();
-        if (tid == 0) chain_publish(chain, a.chain_out + (int)slab0);
-        STGCN_PHASE(4, 15);
-        return;
-    }
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) {
         const int ht = wave + WAVES * q;
@@ -1661,255 +1443,13 @@ __device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int 
 }
 template <int MAXQ, int MAXW, typename ET, int SP>
 __global__ __launch_bounds__(MAXW * 64) void gconv_fwd_kernel(GconvFwdArgs a) {
-    gconv_fwd_body<MAXQ, MAXW, ET, SP>(a, (int)blockIdx.x, (int)blockDim.x, ChainCtl{nullptr, 0, 0u});
+    gconv_fwd_body<MAXQ, MAXW, ET, SP>(a, (int)blockIdx.x, (int)blockDim.x);
 }
 template <int MAXQ, int MAXW>
 __global__ __launch_bounds__(MAXW * 64) void gconv_fwd_b16p_kernel(GconvFwdArgs a) {
-    gconv_fwd_body<MAXQ, MAXW, bf16, 1, true>(a, (int)blockIdx.x, (int)blockDim.x, ChainCtl{nullptr, 0, 0u});
+    gconv_fwd_body<MAXQ, MAXW, bf16, 1, true>(a, (int)blockIdx.x, (int)blockDim.x);
 }
 
-#ifdef STGCN_EXPERIMENTS   // operator-stationary graph conv (opt-in, STGCN_GC_REG=<workgroups per CU>)
-// ================================================================================================
-// F2, persistent operator-stationary form (round 6): ONE workgroup per compute unit walks several (b, t) slabs.
-// The slab-per-workgroup kernel above runs its 1280 / 768 workgroups of C2 as exactly one resident round: all five workgroups of a CU
-// stage X0 together (matrix pipe idle), multiply together and store together -- 19.5 us for 7.2 us of matrix time.  Here
-//   * wave w of workgroup (set, part) owns node tile part + 4 w for the whole launch: the fragments of T_1 .. T_{Ks-1} of THAT tile
-//     (KCH chunks of 1 KiB per term: 26 KiB for the 207-node graph at Ks = 3) are copied ONCE into a wave-private LDS region and
-//     every product reads them from there (the operator crosses L2 -> CU once per workgroup, not once per slab);
-//   * the workgroup walks slabs set, set + S, set + 2 S, ..: X0 of the NEXT slab is requested into registers before the products of the
-//     current one and written to the other LDS buffer behind them -- one barrier per slab, and it does NOT drain vmcnt (barrier_only):
-//     round 2's register-stationary experiment (gconv_fwd_reg_kernel below) put __syncthreads() right behind its prefetch, i.e. waited for
-//     the load it had just issued and for the previous slab's write-through stores in every iteration (4.4 us per slab for 1.8 us of MFMAs);
-//   * the epilogue is the slab kernel's (X_k tiles are at once store layout and A operand of the 16 x 16 weight contraction).
-// grid = 4 * S workgroups of 256 threads (S slab sets, parts = 4: up to 16 node tiles = 256 nodes), LDS = 4 waves x (Ks - 1) x KCH KiB + two
-// transposed X0 buffers (C2: 133 KB: one workgroup per CU).  Same arithmetic, same summation order per element as gconv_fwd_kernel.
-// MEASURED SLOWER (pass r6-09, profiles/r6-09_gconv_fwd_persistent.txt: C2 24.7 + 18.3 us against 21.6 + 14.9 for the slab kernel, results equal,
-// all stage tests green): with ONE wave per SIMD the ~300 VALU / SALU instructions a wave spends per slab outside its 116 MFMAs (X0 commit,
-// fetch addresses, epilogue stores) issue at one per ~7.5 cycles (tools/ubench/overlap.hip) and nothing fills the gaps -- 6.5 k cycles per
-// slab for 3.7 k of matrix time -- while the slab kernel's five co-resident workgroups per CU give every SIMD five waves to interleave.  A second
-// wave group per workgroup does not fit (104 KB of fragments + 4 X0 buffers = the whole LDS) and five slabs per set cut 2 + 2 + 1.  Opt-in
-// (-DSTGCN_EXPERIMENTS, STGCN_GC_PERS=1), like round 2's register-stationary form below.
-// ================================================================================================
-inline size_t gconv_fwd_pers_lds_bytes(int NP, int terms) { return ((size_t)4 * (terms - 1) * (NP / 16) * 256 + (size_t)2 * 16 * (NP + 4)) * sizeof(float); }
-template <typename ET>
-__global__ __launch_bounds__(256) void gconv_fwd_pers_kernel(GconvFwdArgs a, int S) {
-    typedef Mma<ET> MM;
-    extern __shared__ float stgcn_smem[];
-    constexpr int THREADS = 256, NV = 4;   // float4 per thread and slab (NP * 4 <= 1024)
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int part = (int)(blockIdx.x & 3u), set = (int)(blockIdx.x >> 2);
-    const int N = a.N, NP = a.NP, LDX = NP + 4, HT = NP >> 4, KCH = NP >> 4, NT = a.Ks - 1;   // NT operator terms (1 or 2)
-    const size_t MSZ = (size_t)NP * NP;
-    const int ht = part + 4 * w;           // this wave's node tile
-    const bool own = ht < HT;              // (wave-uniform)
-    float* const Fr = stgcn_smem + (size_t)w * NT * KCH * 256;      // [NT][KCH][64 lanes][4]: this wave's operator fragments
-    float* const XTb = stgcn_smem + (size_t)4 * NT * KCH * 256;     // [2][16][LDX]: X0 transposed, two buffers
-    ET* const Xk_ = et_ptr<ET>(a.Xk);
-    ET* const G_ = et_ptr<ET>(a.G);
-    const ET* const A_ = et_ptr<ET>(a.A);
-
-    // ---- X0 slabs: registers (one slab ahead) -> LDS, transposed [c][node] ------------------------------------------------------
-    Raw4<ET> xv[NV];
-    auto fetch = [&](long slab) __attribute__((always_inline)) {   // (unconditional, clamped: a branch around a load resets the compiler's wait counts)
-        const ET* Asl = A_ + (size_t)(slab < a.slabs ? slab : a.slabs - 1) * N * 16;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * THREADS, n = idx >> 2, c4 = idx & 3;
-            xv[i] = ldraw4(Asl + (size_t)(n < N ? n : N - 1) * 16 + c4 * 4);
-        }
-    };
-    auto commit = [&](float* XT) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * THREADS, n = idx >> 2, c4 = idx & 3;
-            if (idx < NP * 4) {
-                const f32x4 v = n < N ? cvt4(xv[i]) : zero4();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) XT[(c4 * 4 + j) * LDX + n] = v[j];
-            }
-        }
-    };
-    fetch(set);
-    // ---- this wave's operator fragments -> its LDS region (lane-linear 16-byte stores: conflict free), in batches of 8 loads ---------
-    if (own) {
-        for (int c0 = 0; c0 < NT * KCH; c0 += 8) {
-            f32x4 fv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int c = c0 + u < NT * KCH ? c0 + u : NT * KCH - 1, k = c / KCH, kc = c - k * KCH;
-                fv[u] = ld4(a.Lp + (size_t)k * MSZ + ((size_t)(ht * KCH + kc) * 64 + lane) * 4);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (c0 + u < NT * KCH) st4(Fr + (size_t)(c0 + u) * 256 + lane * 4, fv[u]);
-        }
-    }
-    // weight fragments B[kk = c][col = j] = W_k[c = 4g + s][j = l15] of the (up to) three terms, bias
-    typename MM::frag wf[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        f32x4 v = zero4();
-        if (k <= NT && !(a.kipf && k == 0)) {
-            const float* Wk = a.W + (a.kipf ? 0 : (size_t)k * 256);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) v[s] = Wk[(4 * g + s) * 16 + l15];
-        }
-        wf[k] = MM::cvt(v);
-    }
-    const float bb = a.bias ? a.bias[l15] : 0.f;
-    commit(XTb);
-    barrier_only();
-
-    int it = 0;
-    for (long slab = set; slab < a.slabs; slab += S, ++it) {
-        const float* const XT0 = XTb + (it & 1) * 16 * LDX;
-        fetch(slab + S);                   // the next slab of this set (clamped beyond the end: never committed)
-        if (own) {
-            const int h = ht * 16 + l15;
-            const f32x4 res = ld4(XT0 + l15 * LDX + ht * 16 + 4 * g);   // residual X0[h = ht*16 + 4g + r][j = l15] (D layout of the weight contraction)
-            f32x4 yacc = MM::mma(MM::cvt(gather4(XT0 + (4 * g) * LDX + h, LDX)), wf[0], zero4());   // term 0: X0 W0
-            f32x4 acc1 = zero4(), acc2 = zero4();
-            if (NT == 2) {
-#pragma unroll 4
-                for (int kc = 0; kc < KCH; ++kc) {
-                    const typename MM::frag af = MM::cvt(ld4(XT0 + l15 * LDX + kc * 16 + 4 * g));   // A[c = l15][node = kc*16 + 4g + s]
-                    MM::mma_b2(af, MM::cvt(ld4(Fr + (size_t)kc * 256 + lane * 4)), MM::cvt(ld4(Fr + (size_t)(KCH + kc) * 256 + lane * 4)), acc1, acc2);
-                }
-            } else {
-#pragma unroll 4
-                for (int kc = 0; kc < KCH; ++kc)
-                    acc1 = MM::mma(MM::cvt(ld4(XT0 + l15 * LDX + kc * 16 + 4 * g)), MM::cvt(ld4(Fr + (size_t)kc * 256 + lane * 4)), acc1);
-            }
-            // acc[r] = X_k[h][c = 4g + r]: store layout and A operand of the weight contraction
-            if (a.Xk && h < N) {
-                stx4_wt(Xk_ + ((size_t)slab * N + h) * 16 + 4 * g, acc1);
-                if (NT == 2) stx4_wt(Xk_ + (((size_t)a.slabs + slab) * N + h) * 16 + 4 * g, acc2);
-            }
-            if (NT == 2) MM::mma_ab2(MM::cvt(acc1), wf[1], MM::cvt(acc2), wf[2], yacc);
-            else yacc = MM::mma(MM::cvt(acc1), wf[1], yacc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int hh = ht * 16 + 4 * g + r;
-                if (hh < N) stx1(G_ + ((size_t)slab * N + hh) * 16 + l15, fmaxf(yacc[r] + bb + res[r], 0.f));
-            }
-        }
-        if (slab + S < a.slabs) commit(XTb + ((it & 1) ^ 1) * 16 * LDX);   // (uniform) the other buffer: its last readers are behind the previous barrier
-        barrier_only();
-    }
-}
-
-// ================================================================================================
-// F2 (operator-stationary variant): the fragments of T_1 .. T_{Ks-1} a wave needs for ITS node tile (KCH chunks per term,
-// 1 KiB each: 26 KiB for the 207-node graph, Ks = 3) are loaded into registers ONCE and the workgroup then walks `spw`
-// slabs: per MFMA of the slab-per-workgroup kernel a wave pulls 256 B of operator through its CU's vector-memory path
-// (~25 B/clk measured, i.e. the four SIMDs together are fed at 78 % of what their MFMAs consume, and every slab re-reads
-// the whole 340 KB operator from L2: 110 MB per launch at C2).  Here the operator crosses the L1 once per workgroup
-// (256 workgroups x 104 KiB), the per-slab traffic is the 13 KiB X0 slab (prefetched into registers one slab ahead,
-// double-buffered in LDS) and the MFMAs are fed from registers (B) and LDS (A).
-// grid = parts * groups; workgroup (part, grp) owns node tiles part + parts * wave and slabs grp*spw .. +spw.
-// Template: KCM >= KCH chunks per term held in registers, NTERM = Ks - 1 (1 or 2) operator terms.
-// ================================================================================================
-template <int KCM, int NTERM>
-__global__ __launch_bounds__(256) void gconv_fwd_reg_kernel(GconvFwdArgs a, int spw) {
-    extern __shared__ float stgcn_smem[];
-    constexpr int THREADS = 256;
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
-    const int P = a.parts, part = (int)(blockIdx.x % (unsigned)P);
-    const long grp = blockIdx.x / (unsigned)P;
-    const int N = a.N, NP = a.NP, LDX = NP + 4, HT = NP >> 4, KCH = NP >> 4;
-    const size_t MSZ = (size_t)NP * NP;
-    const int ht = part + P * (tid >> 6);   // this wave's node tile
-    const bool own = ht < HT;
-    const long s0 = grp * spw;
-    long s1 = s0 + spw;
-    if (s1 > a.slabs) s1 = a.slabs;
-
-    // ---- operator fragments of this wave's tile -> registers, weight fragments, bias -------------------------------
-    f32x4 Tr[NTERM][KCM];
-#pragma unroll
-    for (int k = 0; k < NTERM; ++k)
-#pragma unroll
-        for (int kc = 0; kc < KCM; ++kc)
-            Tr[k][kc] = (own && kc < KCH) ? ld4(a.Lp + (size_t)k * MSZ + ((size_t)(ht * KCH + kc) * 64 + lane) * 4) : zero4();
-    f32x4 wf[NTERM + 1];   // B[kk = c][col = j] = W_k[c = 4g + s][j = l15]
-#pragma unroll
-    for (int k = 0; k <= NTERM; ++k) {
-        wf[k] = zero4();
-        if (!(a.kipf && k == 0)) {
-            const float* Wk = a.W + (a.kipf ? 0 : (size_t)k * 256);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) wf[k][s] = Wk[(4 * g + s) * 16 + l15];
-        }
-    }
-    const float bb = a.bias ? a.bias[l15] : 0.f;
-
-    // ---- X0 slabs: registers (one slab ahead) -> LDS (two buffers), transposed [c][node] -------------------------------
-    constexpr int NV = 4;   // float4 per thread per slab (NP * 4 <= 1024, i.e. N <= 256)
-    f32x4 xv[NV];
-    auto fetch = [&](long slab) {
-        const float* Asl = a.A + (size_t)slab * N * 16;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * THREADS, n = idx >> 2, c4 = idx & 3;
-            xv[i] = (idx < NP * 4 && n < N) ? ld4(Asl + (size_t)n * 16 + c4 * 4) : zero4();
-        }
-    };
-    auto commit = [&](float* XT) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * THREADS, n = idx >> 2, c4 = idx & 3;
-            if (idx < NP * 4) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) XT[(c4 * 4 + j) * LDX + n] = xv[i][j];
-            }
-        }
-    };
-    if (s0 < s1) {
-        fetch(s0);
-        commit(stgcn_smem);
-    }
-    for (long slab = s0; slab < s1; ++slab) {
-        float* const XT0 = stgcn_smem + ((slab - s0) & 1) * 16 * LDX;
-        float* const XTn = stgcn_smem + (((slab - s0) & 1) ^ 1) * 16 * LDX;
-        if (slab + 1 < s1) fetch(slab + 1);
-        __syncthreads();   // XT0 complete; every wave is past its reads of XTn (previous slab)
-        if (own) {
-            const int h = ht * 16 + l15;
-            // residual X0[h = ht*16 + 4g + r][j = l15]  (D layout of the weight contraction)
-            const f32x4 res = ld4(XT0 + l15 * LDX + ht * 16 + 4 * g);
-            f32x4 yacc = zero4();
-#pragma unroll
-            for (int s = 0; s < 4; ++s) yacc = mfma4(XT0[(4 * g + s) * LDX + h], wf[0][s], yacc);   // term 0: X0 W0
-            f32x4 acc[NTERM];
-#pragma unroll
-            for (int k = 0; k < NTERM; ++k) acc[k] = zero4();
-#pragma unroll
-            for (int kc = 0; kc < KCM; ++kc) {
-                if (kc < KCH) {
-                    const f32x4 af = ld4(XT0 + l15 * LDX + kc * 16 + 4 * g);   // A[c = l15][node = kc*16 + 4g + s]
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int k = 0; k < NTERM; ++k) acc[k] = mfma4(af[s], Tr[k][kc][s], acc[k]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < NTERM; ++k) {   // acc[k][r] = X_{k+1}[h][c = 4g + r]
-                if (a.Xk && h < N) st4_wt(a.Xk + (((size_t)k * a.slabs + slab) * N + h) * 16 + 4 * g, acc[k]);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) yacc = mfma4(acc[k][s], wf[k + 1][s], yacc);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int hh = ht * 16 + 4 * g + r;
-                if (hh < N) a.G[((size_t)slab * N + hh) * 16 + l15] = fmaxf(yacc[r] + bb + res[r], 0.f);
-            }
-        }
-        if (slab + 1 < s1) commit(XTn);
-    }
-}
-
-#endif  // STGCN_EXPERIMENTS
 
 // ================================================================================================
 // F4: LayerNorm over the joint [N, C] axes of each (b, t) slab (biased variance, eps 1e-12,

@@ -69,7 +69,7 @@ inline size_t tc2_bwd_lds_bytes(int C2, int Kt, int T1, int T2, bool recomp = tr
 // RECOMP costs KT more product steps per 16 output channels and step: + 50 % matrix work in this kernel.  Measured on MI355X
 // (profiles/r3-02_*): with fp32 products the CUs that hold two workgroups become MFMA-bound (C2: 27.3 -> 34.0 us, 18.2 -> 21.6 us per
 // launch, more than tc2_ln_fwd and the hooks gain), with bf16 products the step gains 5 % (C3: 0.790 -> 0.753 ms).  The host therefore
-// recomputes for bf16 activations and reads the stored gate inputs for fp32 (STGCN_TC2_RECOMP=0/1 overrides).
+// recomputes for bf16 activations and reads the stored gate inputs for fp32.
 // With one wave of each kind on a SIMD the E wave's memory / LDS latencies are covered by the M wave's instructions and vice versa, which a single
 // wave walking E then M cannot do (phase stamps of the one-role version: 3.7 k cycles per step for 1.5 k cycles of MFMAs).  (Round 6, tools/ubench/overlap.hip:
 // the fp32 MFMA and the VALU of a SIMD do NOT execute side by side -- the gain is latency hiding, the SIMD's time is the sum of both streams.)  The ring has a
@@ -1237,7 +1237,6 @@ struct Tc1FwdArgs {
     float* S;
     float* A;                 // [B][T1][N][16]
     int B, T, T1, N, node_tiles;
-    int chain_out;            // chained launch: counter chain_out + b * T1 + t counts the node tiles of A[b][t] written (-1: none)
 };
 inline size_t tc1_fwd_lds_bytes(int CIN, int Kt, bool x6 = false) {
     // x tiles: fp32 rows, or (X6) three bf16 planes per tile; then the partial Align tiles
@@ -1245,14 +1244,13 @@ inline size_t tc1_fwd_lds_bytes(int CIN, int Kt, bool x6 = false) {
     return ring + (size_t)2 * 4 * 16 * 20 * sizeof(float);
 }
 
-// bid / nb: this workgroup's index among the nb workgroups of the role (the kernel's own grid, or the role's share of a chained launch);
-// chain.words != null: every A tile is published on counter chain_out + b * T1 + t (node_tiles arrivals complete a slab)
+// bid / nb: this workgroup's index among the nb workgroups of the launch
 // X6 (round 6, fp32 blocks only): the conv product as "bf16x6" -- fp32-accurate products on the bf16 matrix pipe (Frag3, stgcn_device.hip.h).
 // The E waves split every x tile into three bf16 planes when they stage it (once per tile: it then serves KT taps of four M waves); the M
 // waves split their stationary weights once; the product loop reads plane triples and issues 3 x v_mfma_f32_16x16x32_bf16 per 16-deep step
 // instead of 4 x v_mfma_f32_16x16x4_f32, with no conversion in the loop.  The small Align product stays on fp32 MFMAs.
 template <int C0, int CIN, int KT, int ACT, typename ET, bool X6 = false>
-__device__ __forceinline__ void tc1_fwd_body(const Tc1FwdArgs& a, const int bid, const int nb, const ChainCtl& chain) {
+__device__ __forceinline__ void tc1_fwd_body(const Tc1FwdArgs& a, const int bid, const int nb) {
     static_assert(C0 == 64 && (CIN == 16 || CIN == 32 || CIN == 64), "shapes covered by the role split below");
     static_assert(!X6 || std::is_same<ET, float>::value, "bf16x6 is a product form of the fp32 blocks");
     typedef Mma<ET> MM;
@@ -1274,7 +1272,6 @@ __device__ __forceinline__ void tc1_fwd_body(const Tc1FwdArgs& a, const int bid,
     const long u_lo = units * (long)bid / (long)nb, u_hi = units * ((long)bid + 1) / (long)nb;
     const long item0 = u_lo / T1, item1 = u_hi / T1;
     const int s0 = (int)(u_lo - item0 * T1), s1 = (int)(u_hi - item1 * T1);
-    const bool chained = chain.words != nullptr && a.chain_out >= 0;
     STGCN_PHASE(11, 0);
 #ifdef STGCN_PHASE_TIMING   // (diagnostic build: thread 0 = M wave 0; cycles of MFMA issue / epilogue / barrier wait / item transitions, tools/gpu_phases.py kid 11)
     long long pt_mma = 0, pt_epi = 0, pt_wait = 0, pt_a = 0, pt_b = 0, pt_c = 0, pt_steps = 0, pt_trans = 0;
@@ -1393,18 +1390,12 @@ __device__ __forceinline__ void tc1_fwd_body(const Tc1FwdArgs& a, const int bid,
                     if (cq < CIN / 4) st4(Xs + (size_t)(xt % RING) * 16 * LDXS + r * LDXS + 4 * cq, v);
                 }
             };
-            // A[t] = sum of the 4 waves' partial tiles + bias: ONE wave, 16 bytes per lane, written through (round 3: 256 scalar stores).  In a
-            // chained launch the wave then drains its stores and bumps the slab's arrival counter: the graph conv of slab (b, t) starts when
-            // all node tiles have arrived, while this workgroup walks on.
+            // A[t] = sum of the 4 waves' partial tiles + bias: ONE wave, 16 bytes per lane, written through (round 3: 256 scalar stores)
             auto F = [&](int t) {
                 if (tid >= 64) return;   // (wave-uniform)
                 const float* rd = red + (t & 1) * RED + fr * 20 + 4 * fq;
                 const f32x4 v = ((ld4(rd) + ld4(rd + 16 * 20)) + (ld4(rd + 2 * 16 * 20) + ld4(rd + 3 * 16 * 20))) + bj;
                 if (n0 + fr < N) stx4_wt(A_ + (((size_t)b * T1 + t) * N + n0 + fr) * 16 + 4 * fq, v);
-                if (chained) {
-                    chain_drain_stores();
-                    if (lane == 0) chain_publish(chain, a.chain_out + b * T1 + t);
-                }
             };
             Raw4<ET> xs[KT];
 #pragma unroll
@@ -1433,11 +1424,11 @@ __device__ __forceinline__ void tc1_fwd_body(const Tc1FwdArgs& a, const int bid,
 }
 template <int C0, int CIN, int KT, int ACT, typename ET>
 __global__ __launch_bounds__(512) void tc1_fwd_kernel(Tc1FwdArgs a) {
-    tc1_fwd_body<C0, CIN, KT, ACT, ET>(a, (int)blockIdx.x, (int)gridDim.x, ChainCtl{nullptr, 0, 0u});
+    tc1_fwd_body<C0, CIN, KT, ACT, ET>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 template <int C0, int CIN, int KT, int ACT>
 __global__ __launch_bounds__(512) void tc1_fwd_x6_kernel(Tc1FwdArgs a) {
-    tc1_fwd_body<C0, CIN, KT, ACT, float, true>(a, (int)blockIdx.x, (int)gridDim.x, ChainCtl{nullptr, 0, 0u});
+    tc1_fwd_body<C0, CIN, KT, ACT, float, true>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 // (Round 4, pass r4-06: the same body under __launch_bounds__(512, 4) -- 128 VGPRs, two workgroups REALLY sharing a CU; the plain fp32
 //  CIN = 64 instance takes 133 VGPRs = 3 waves per SIMD, so "two per CU" had been two rounds of one -- measured 28.5 -> 30.5 us: the fp32
@@ -1469,8 +1460,6 @@ struct Tc2LnFwdArgs {
     float* mean;           // [B*T2]
     float* rstd;
     int T1, T2, N, NPR, act, training;   // NPR = roundup16(N)
-    int chain_in;          // chained launch: counter chain_in + b * T1 + t counts the parts of G[b][t] written (chain_expect of them); -1: none
-    unsigned chain_expect;
     float eps, keep_scale;
     uint32_t thresh;
     uint64_t seed, offset;
@@ -1485,7 +1474,7 @@ inline size_t tc2_ln_fwd_lds_bytes(int Kt, int N, bool x6 = false) {
     return (x6 ? (size_t)Kt * 3 * NPR * kLdGh * sizeof(short) : (size_t)Kt * NPR * kLdG * sizeof(float)) + 64 * sizeof(float);
 }
 
-// bid = the (b, t2) slab of this workgroup; chained launch: the KT input slabs G[b][t2 + tap] are awaited on counters chain_in + b * T1 + t2 + tap
+// bid = the (b, t2) slab of this workgroup
 // PP > 1 (round 6): PP workgroups share a slab, each owns a contiguous range of its node tiles (the per-slab chain -- staging, tile passes,
 // statistics, normalise -- is what a launch of few slabs costs, whatever the batch: 15 us per workgroup at 207 nodes, half the chip idle
 // when block 1 offers 128 slabs).  Slab and part come from a start-order TICKET (peers hold consecutive tickets: a workgroup only ever
@@ -1495,7 +1484,7 @@ inline size_t tc2_ln_fwd_lds_bytes(int Kt, int N, bool x6 = false) {
 // are staged (once per slab; every row then serves the four channel-tile waves), the weights once per wave; on a SIMD whose time is the SUM
 // of its fp32 MFMA and VALU cycles this takes the matrix part off the VALU lanes (a bf16 MFMA runs beside them).
 template <int C2, int KT, int NTI, int HV, int PP, typename ET, bool X6 = false>
-__device__ __forceinline__ void tc2_ln_fwd_body(const Tc2LnFwdArgs& a, const int bid, const ChainCtl& chain) {
+__device__ __forceinline__ void tc2_ln_fwd_body(const Tc2LnFwdArgs& a, const int bid) {
     static_assert(C2 == 64, "wave pairing below assumes 4 channel tiles per half");
     static_assert(!X6 || std::is_same<ET, float>::value, "bf16x6 is a product form of the fp32 blocks");
     typedef Mma<ET> MM;
@@ -1532,21 +1521,9 @@ __device__ __forceinline__ void tc2_ln_fwd_body(const Tc2LnFwdArgs& a, const int
     // this workgroup's node tiles [tile0, tile0 + ntiles) of the slab's NPR / 16 (balanced cut), staged as NPR = 16 * ntiles local rows
     const int alltiles = a.NPR >> 4, tile0 = PP > 1 ? part * alltiles / PP : 0, ntiles = PP > 1 ? (part + 1) * alltiles / PP - tile0 : alltiles;
     const int NPR = ntiles << 4, row0 = tile0 << 4;
-    const bool cin = chain.words != nullptr && a.chain_in >= 0;
 
     // stage this workgroup's rows of the KT input slabs G[b][t2 + tap] (zero rows beyond N)
     const ET* Gb = et_ptr<ET>(a.G) + ((size_t)b * a.T1 + t2) * N * 16;
-    if (cin) {   // (the weight loads above are in flight while the last of the KT slabs arrives)
-#pragma unroll
-        for (int tap = 0; tap < KT; ++tap) chain_wait(chain, a.chain_in + b * a.T1 + t2 + tap, a.chain_expect);
-        for (int idx = tid; idx < KT * NPR * 4; idx += 256 * HV) {
-            const int q = idx & 3, rr = (idx >> 2) % NPR, tap = (idx >> 2) / NPR, gr = row0 + rr;
-            const int eo = (tap * N + (gr < N ? gr : N - 1)) * 16 + 4 * q;
-            const f32x4 v = cvt4(ldraw4_sc1(Gb, (long)KT * N * 16, eo));
-            if constexpr (X6) st_frag3(Gh + ((size_t)tap * 3 * NPR + rr) * kLdGh + 4 * q, NPR * kLdGh, split3(gr < N ? v : zero4()));
-            else st4(Gs + ((size_t)tap * NPR + rr) * kLdG + 4 * q, gr < N ? v : zero4());
-        }
-    } else
     for (int idx = tid; idx < KT * NPR * 4; idx += 256 * HV) {
         const int q = idx & 3, rr = (idx >> 2) % NPR, tap = (idx >> 2) / NPR, gr = row0 + rr;
         const f32x4 v = gr < N ? ldx4(Gb + ((size_t)tap * N + gr) * 16 + 4 * q) : zero4();
@@ -1787,37 +1764,11 @@ __device__ __forceinline__ void tc2_ln_fwd_body(const Tc2LnFwdArgs& a, const int
 }
 template <int C2, int KT, int NTI, int HV, int PP, typename ET>
 __global__ __launch_bounds__(256 * HV) void tc2_ln_fwd_kernel(Tc2LnFwdArgs a) {
-    tc2_ln_fwd_body<C2, KT, NTI, HV, PP, ET>(a, (int)blockIdx.x, ChainCtl{nullptr, 0, 0u});
+    tc2_ln_fwd_body<C2, KT, NTI, HV, PP, ET>(a, (int)blockIdx.x);
 }
 template <int C2, int KT, int NTI, int HV, int PP>
 __global__ __launch_bounds__(256 * HV) void tc2_ln_fwd_x6_kernel(Tc2LnFwdArgs a) {
-    tc2_ln_fwd_body<C2, KT, NTI, HV, PP, float, true>(a, (int)blockIdx.x, ChainCtl{nullptr, 0, 0u});
+    tc2_ln_fwd_body<C2, KT, NTI, HV, PP, float, true>(a, (int)blockIdx.x);
 }
-
-// ================================================================================================
-// Chained forward of one ST block (stgcn_device.hip.h "Chained launches"): tmp_conv1 + Align (role 1, n1 workgroups of 512 threads walking the
-// time axis) -> graph conv (role 2, n2 = slabs x parts workgroups of gc_threads threads, slab (b, t) as soon as its node tiles have
-// arrived) [-> tmp_conv2 + LayerNorm + dropout (role 3, one workgroup of 1024 threads per output slab, as soon as its KT input slabs have
-// arrived)] in ONE launch.  Roles and items come from the ticket; waves beyond a role's width leave at once (a finished wave does not take
-// part in s_barrier); every workgroup reserves the widest role's threads and LDS.
-// ================================================================================================
-#ifdef STGCN_EXPERIMENTS
-template <int CIN, int KT, int NTI, bool WITH_TC2, typename ET>
-__global__ __launch_bounds__(WITH_TC2 ? 1024 : 512) void stblock_fwd_chain_kernel(Tc1FwdArgs a1, GconvFwdArgs a2, Tc2LnFwdArgs a3, ChainCtl chain, int n1, int n2,
-                                                                                   int gc_threads, int slot) {
-    extern __shared__ float stgcn_smem[];
-    const int vb = chain_enter(chain, reinterpret_cast<unsigned*>(stgcn_smem) + slot);
-    if (vb < n1) {
-        if (threadIdx.x >= 512) return;
-        tc1_fwd_body<64, CIN, KT, 0, ET>(a1, vb, n1, chain);
-    } else if (vb < n1 + n2) {
-        if ((int)threadIdx.x >= gc_threads) return;
-        gconv_fwd_body<1, 16, ET, 1>(a2, vb - n1, gc_threads, chain);
-    } else {
-        if constexpr (WITH_TC2) tc2_ln_fwd_body<64, KT, NTI, 4, 1, ET>(a3, vb - n1 - n2, chain);
-    }
-    chain_exit(chain);
-}
-#endif
 
 }  // namespace stgcn

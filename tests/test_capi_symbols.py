@@ -89,5 +89,5 @@ def test_no_kernel_of_the_library_uses_scratch():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and int(m.group(1)) > 0:
             bad.append((name, int(m.group(1))))
-    # (no exceptions since round 5: the one kernel that spilled -- the fp32 three-role chained launch of round 4 -- left the product build)
+    # (no exceptions since round 5: the one kernel that spilled -- the fp32 three-role chained launch of round 4 -- was removed)
     assert not bad, bad

@@ -39,19 +39,6 @@ def test_graph_conv_slab_parts(parts):
 
 
 @pytest.mark.full
-def test_time_complete_conv_tiles():
-    # opt-in gated conv with one workgroup per (window, 16 nodes) over all time steps (tconv_fwd3_kernel)
-    run_subset({"STGCN_TCONV_V": "3"}, [FWD], "17-1-6 or 35-1-5 or 300-6-12")
-
-
-@pytest.mark.full
-@pytest.mark.parametrize("per_cu", [1, 3])
-def test_operator_stationary_graph_conv(per_cu):
-    # opt-in graph conv with a wave's operator fragments in registers over several slabs (gconv_fwd_reg_kernel)
-    run_subset({"STGCN_GC_REG": str(per_cu)}, [FWD], "17-1-6 or 35-1-5 or 9-2-5")
-
-
-@pytest.mark.full
 def test_head_tap_masked_kernels():
     # the row-tile kernels the output head used before the dense 32 x 256 tiles (tconv_fwd4_kernel) stay selectable
     run_subset({"STGCN_TCONV4": "0"}, ["tests/test_emu_head.py"], "head")
