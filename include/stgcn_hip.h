@@ -30,9 +30,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8).  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9).  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
-#define STGCN_ABI_VERSION 8
+#define STGCN_ABI_VERSION 9
 
 #define STGCN_OK 0
 #define STGCN_ERR_UNSUPPORTED 1 /* shape outside what the kernels cover (message says which) */
@@ -75,10 +75,17 @@ typedef struct stgcn_stblock_desc {
      * times; here the first block can read its windows straight from the resident (time, N) series): window b of `x` starts
      * x_bstride ROWS (of c_in floats) after window b-1 (0 = dense, T*N; N = windows one time step apart), and the whole input
      * is shifted by *x_index_dev * x_index_stride floats (nullable: the batch position of a captured training step).
-     * Only for blocks whose input needs no gradient (need_dx = 0).                                                          */
+     * Only for blocks whose input needs no gradient (need_dx = 0).
+     * x_window_dev (nullable; shuffled epochs): a device table of window starts.  With it, window b starts
+     * x_window_dev[*x_index_dev + b] * x_index_stride floats into `x` -- the batch position selects a run of B table entries instead
+     * of a run of B consecutive windows -- and x_bstride is ignored.  It needs x_index_dev != NULL, need_dx = 0 and
+     * 0 < x_index_stride < 2^31 a multiple of c_in (windows start on whole rows of the series); the caller keeps
+     * *x_index_dev + B within the table and every window inside the buffer behind `x` (nothing on the device checks either).
+     * Without a table every kernel takes exactly the path it takes for x_bstride / x_index_dev alone.                         */
     int64_t x_bstride;
     const int64_t* x_index_dev;
     int64_t x_index_stride;
+    const int64_t* x_window_dev;
     int32_t dy_rowstats_ready; /* backward: 1 = the kernel that produced `dy` already wrote this block's LayerNorm-backward row partials
                                   (stgcn_ln_hook handed to that producer's backward call); the block skips its own pass over dy          */
     int32_t dtype;            /* STGCN_DTYPE_*                                                                               */
@@ -332,12 +339,15 @@ typedef struct stgcn_outblock_grads {
  * 2 (pred - target) / n * grad_scale is formed inside the fc backward kernel instead of being read, and the loss value comes out of the
  * call's gradient reduction -- no separate loss launch.  pred = the (B, T1, N) output the forward of the same call chain wrote
  * (n = B*T1*N values, end_channel = 1); target: n floats, read at target + *target_index_dev * target_index_stride when an index is
- * given (device-side windowing, as in stgcn_mse_loss_grad).                                                                            */
+ * given (device-side windowing, as in stgcn_mse_loss_grad).  With target_window_dev (nullable, needs target_index_dev; the table of
+ * desc.x_window_dev when `target` is the series shifted by n_his + n_pred - 1 rows) the T1*N labels of window b are read at
+ * target + target_window_dev[*target_index_dev + b] * target_index_stride instead.                                                     */
 typedef struct stgcn_head_loss {
     const float* pred;
     const float* target;
     const int64_t* target_index_dev;   /* nullable */
     int64_t target_index_stride;
+    const int64_t* target_window_dev;  /* nullable */
     float grad_scale;                  /* e.g. 1 / world, or the tail-batch weight */
     int32_t reserved;
 } stgcn_head_loss;
@@ -487,6 +497,13 @@ int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, co
  *      target + *target_index_dev * target_index_stride floats (nullable: labels taken from the resident series).        */
 int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
                         const int64_t* target_index_dev, int64_t target_index_stride, void* stream);
+/*      The same with a window table (shuffled epochs, stgcn_stblock_desc.x_window_dev): the n values are n / window_floats windows of
+ *      window_floats labels each, and window b is read at target + target_window_dev[*target_index_dev + b] * target_index_stride.
+ *      target_window_dev == NULL: stgcn_mse_loss_grad itself.  (window_floats: the one value the table form needs that the argument
+ *      list above does not carry.)                                                                                        */
+int stgcn_mse_loss_grad_windows(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
+                                const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
+                                int64_t window_floats, void* stream);
 
 /* ---- Evaluation: the sums behind script/utility.py:90-101 (evaluate_model: MSE in z-scored units) and :103-121 (evaluate_metric: MAE,
  *      RMSE, WMAPE after the scaler's inverse transform), formed on the device, one launch per minibatch, into a caller-owned state of

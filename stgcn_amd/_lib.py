@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libstgcn_hip.so")
 
 STGCN_OK = 0
-ABI_VERSION = 8      # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
+ABI_VERSION = 9      # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
 ACT = {"glu": 0, "gtu": 1}
 GRAPH_CONV = {"cheb_graph_conv": 0, "graph_conv": 1}
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -30,7 +30,7 @@ class StblockDesc(C.Structure):
                 ("act", C.c_int32), ("graph_conv", C.c_int32), ("training", C.c_int32),
                 ("droprate", C.c_float), ("ln_eps", C.c_float), ("need_dx", C.c_int32), ("reserved", C.c_int32),
                 ("prepacked", C.c_int32), ("defer_reduce", C.c_int32),
-                ("x_bstride", C.c_int64), ("x_index_dev", C.c_void_p), ("x_index_stride", C.c_int64),
+                ("x_bstride", C.c_int64), ("x_index_dev", C.c_void_p), ("x_index_stride", C.c_int64), ("x_window_dev", C.c_void_p),
                 ("dy_rowstats_ready", C.c_int32), ("dtype", C.c_int32)]
 
 
@@ -87,7 +87,7 @@ class OutblockGrads(C.Structure):      # stgcn_outblock_grads: the parameter gra
 
 class HeadLoss(C.Structure):           # stgcn_head_loss
     _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("target_index_dev", C.c_void_p), ("target_index_stride", C.c_int64),
-                ("grad_scale", C.c_float), ("reserved", C.c_int32)]
+                ("target_window_dev", C.c_void_p), ("grad_scale", C.c_float), ("reserved", C.c_int32)]
 
 
 HEAD_PLAN_FIELDS = ["T1", "rows", "rows_in", "out_floats", "saved_floats", "ws_floats", "sv_U", "sv_S", "sv_mean", "sv_rstd", "sv_yln",
@@ -223,6 +223,9 @@ class _Lib:
         d.stgcn_mse_loss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p]
         d.stgcn_mse_loss_grad.restype = C.c_int
+        d.stgcn_mse_loss_grad_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_int64, C.c_void_p]
+        d.stgcn_mse_loss_grad_windows.restype = C.c_int
         d.stgcn_eval_arm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         d.stgcn_eval_arm.restype = C.c_int
         d.stgcn_eval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -269,7 +272,7 @@ def lib() -> _Lib:
 EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn_stblock_plan_query", "stgcn_gso_prepare",
                     "stgcn_stblock_forward", "stgcn_stblock_backward", "stgcn_dropout_mask", "stgcn_profile_enable",
                     "stgcn_profile_collect", "stgcn_outblock_plan_query", "stgcn_outblock_forward", "stgcn_outblock_backward", "stgcn_adamw_step", "stgcn_prepack",
-                    "stgcn_mse_loss_grad", "stgcn_grad_flush", "stgcn_gso_layout", "stgcn_set_gc_tiled_min_nodes",
+                    "stgcn_mse_loss_grad", "stgcn_mse_loss_grad_windows", "stgcn_grad_flush", "stgcn_gso_layout", "stgcn_set_gc_tiled_min_nodes",
                     "stgcn_set_gc_precision", "stgcn_set_gc_ld_pad", "stgcn_set_debug_stages",
                     "stgcn_stblock_ln_hook", "stgcn_stblock_backward_hook", "stgcn_outblock_backward_hook", "stgcn_set_tc1_bwd_wgs",
                     "stgcn_set_slab_gc_precision", "stgcn_outblock_backward_loss", "stgcn_set_bwd_precision", "stgcn_set_gemm_big_nt",

@@ -162,6 +162,11 @@ int check_desc(const stgcn_stblock_desc* d) {
     if ((d->c_in & 3) != 0 && d->Kt * d->c_in > 16)
         return fail(STGCN_ERR_UNSUPPORTED, "c_in=%d: input channels must be a multiple of 4 unless Kt*c_in <= 16", d->c_in);
     if (d->dtype != STGCN_DTYPE_F32 && d->dtype != STGCN_DTYPE_BF16) return fail(STGCN_ERR_INVALID, "dtype must be STGCN_DTYPE_F32 or STGCN_DTYPE_BF16");
+    if (d->x_window_dev && (!d->x_index_dev || d->need_dx))
+        return fail(STGCN_ERR_INVALID, "x_window_dev (window table) needs x_index_dev != NULL and need_dx = 0");
+    if (d->x_window_dev && (d->x_index_stride <= 0 || d->x_index_stride >= (1ll << 31) || d->x_index_stride % d->c_in != 0))
+        return fail(STGCN_ERR_INVALID, "x_window_dev: x_index_stride = %lld must be a positive multiple of c_in = %d below 2^31",
+                    (long long)d->x_index_stride, d->c_in);
     if (d->x_bstride < 0 || ((d->x_bstride != 0 || d->x_index_dev) && d->need_dx))
         return fail(STGCN_ERR_INVALID, "strided / indexed input windows (x_bstride, x_index_dev) need need_dx = 0 and x_bstride >= 0");
     return STGCN_OK;
@@ -1213,7 +1218,7 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
         ThinFwdArgs f;
         memset(&f, 0, sizeof(f));
         f.ts.src = x; f.ts.C = d->c_in; f.ts.taps = d->Kt; f.ts.N = d->N; f.ts.Tsrc = d->T; f.ts.Tdst = v.T1; f.ts.dir = 1; f.ts.rows = v.rows1;
-        f.ts.bstride = d->x_bstride; f.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); f.ts.idx_stride = d->x_index_stride;
+        f.ts.bstride = d->x_bstride; f.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); f.ts.idx_stride = d->x_index_stride; f.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
         f.Wd = ws + pl.ws_W1dense; f.bias = ws + pl.ws_b1; f.Wap = ws + pl.ws_Wap; f.ba = ws + pl.ws_ba; f.A = saved + pl.sv_A;
         if (fuse_pack) {
             // ONE launch: the layer (operands straight from the parameters) + the parked pack jobs (pack_thin_fwd_kernel)
@@ -1239,7 +1244,7 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
         memset(&t1, 0, sizeof(t1));
         t1.ts.src = x; t1.ts.C = d->c_in; t1.ts.taps = d->Kt; t1.ts.N = d->N; t1.ts.Tsrc = d->T; t1.ts.Tdst = v.T1; t1.ts.dir = 1;
         t1.ts.rows = v.rows1;
-        t1.ts.bstride = d->x_bstride; t1.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); t1.ts.idx_stride = d->x_index_stride;
+        t1.ts.bstride = d->x_bstride; t1.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); t1.ts.idx_stride = d->x_index_stride; t1.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
         t1.Wp = ws + pl.ws_W1p; t1.bias = ws + pl.ws_b1; t1.KCH = v.KP1 / 16; t1.Cout = d->c0; t1.act = d->act;
         t1.U = pl.recompute_tc1 ? nullptr : saved + pl.sv_U1; t1.S = pl.recompute_tc1 ? nullptr : saved + pl.sv_S1; t1.H = nullptr;
         t1.Wap = ws + pl.ws_Wap; t1.ba = ws + pl.ws_ba; t1.A = saved + pl.sv_A; t1.c1 = d->c1;

@@ -161,7 +161,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         a.dA = ws + pl.ws_dA; a.Wd = ws + pl.ws_W1dense; a.bias = ws + pl.ws_b1; a.WaT = ws + pl.ws_WaT;
         a.dZ = d->need_dx ? ws + pl.ws_dZ1 : nullptr; a.part = part + bg.off_al; a.rows = v.rows1; a.c0 = d->c0; a.act = d->act;
         a.ts.src = x; a.ts.C = d->c_in; a.ts.taps = d->Kt; a.ts.N = d->N; a.ts.Tsrc = d->T; a.ts.Tdst = v.T1; a.ts.dir = 1; a.ts.rows = v.rows1;
-        a.ts.bstride = d->x_bstride; a.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); a.ts.idx_stride = d->x_index_stride;
+        a.ts.bstride = d->x_bstride; a.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); a.ts.idx_stride = d->x_index_stride; a.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
         if (thin_wave_tiles()) {   // wave-per-tile form (stgcn_kernels_thin.hip.h): same arguments, same partials
             if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ETB("align_gate_bwd", st, (thin_tc1_bwd2_kernel<ET, 0>), dim3(bg.al_wgs), dim3(kThreads), thin_bwd2_lds_bytes(), a);
             else STGCN_LAUNCH_ETB("align_gate_bwd", st, (thin_tc1_bwd2_kernel<ET, 1>), dim3(bg.al_wgs), dim3(kThreads), thin_bwd2_lds_bytes(), a);
@@ -177,7 +177,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         if (pl.recompute_tc1) {
             a.U = nullptr; a.S = nullptr; a.Wd = ws + pl.ws_W1dense; a.bias = ws + pl.ws_b1; a.KPd = v.KP1;
             a.ts.src = x; a.ts.C = d->c_in; a.ts.taps = d->Kt; a.ts.N = d->N; a.ts.Tsrc = d->T; a.ts.Tdst = v.T1; a.ts.dir = 1; a.ts.rows = v.rows1;
-            a.ts.bstride = d->x_bstride; a.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); a.ts.idx_stride = d->x_index_stride;
+            a.ts.bstride = d->x_bstride; a.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); a.ts.idx_stride = d->x_index_stride; a.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
         } else {
             a.U = saved + pl.sv_U1; a.S = saved + pl.sv_S1;
         }
@@ -193,7 +193,7 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
         memset(&wa, 0, sizeof(wa));
         wa.ts.taps = d->Kt; wa.ts.N = d->N; wa.ts.dir = 1;
         wa.ts.src = x; wa.ts.C = d->c_in; wa.ts.Tsrc = d->T; wa.ts.Tdst = v.T1; wa.ts.rows = v.rows1;
-        wa.ts.bstride = d->x_bstride; wa.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); wa.ts.idx_stride = d->x_index_stride;
+        wa.ts.bstride = d->x_bstride; wa.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); wa.ts.idx_stride = d->x_index_stride; wa.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
         wa.dZ = ws + pl.ws_dZ1; wa.part = part + bg.w1.off; wa.NC = v.NC1; wa.Mpad = bg.w1.Mpad; wa.rows_per_chunk = bg.w1.rows_per_chunk;
         wa.chunks = bg.w1.chunks;
         rc = launch_bwd_weight("tconv_bwd_weight.tc1", wa, bg.w1, st);

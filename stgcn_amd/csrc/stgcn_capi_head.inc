@@ -398,6 +398,8 @@ int stgcn_outblock_backward_loss(const stgcn_outblock_desc* d, const stgcn_outbl
                                  void* stream) {
     if (!hl || !hl->pred || !hl->target) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: NULL pred / target");
     if (!G || !G->loss) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: grads->loss is NULL");
+    if (hl->target_window_dev && !hl->target_index_dev)
+        return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: target_window_dev (window table) needs target_index_dev != NULL");
     return outblock_backward_impl(d, P, x, nullptr, hl, saved, ws, G, dx, dx_hook, stream);
 }
 } // extern "C"
@@ -434,6 +436,7 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         if (hl) {
             a.pred = hl->pred; a.target = hl->target; a.target_index = reinterpret_cast<const long*>(hl->target_index_dev);
             a.target_index_stride = (long)hl->target_index_stride; a.loss_scale = hl->grad_scale;
+            a.target_window = reinterpret_cast<const long*>(hl->target_window_dev); a.target_window_elems = (unsigned)(g.rows / d->B);
         }
         if (own_rowstats) {   // the head's LayerNorm-backward row partials in this kernel's epilogue (dyln is that LayerNorm's output gradient)
             a.rs.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b); a.rs.U = saved + pl.sv_U; a.rs.S = saved + pl.sv_S; a.rs.gamma = P->ln_w;
@@ -710,7 +713,25 @@ int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float
     if (!pred || !target || !loss || !dpred || n < 1) return fail(STGCN_ERR_INVALID, "stgcn_mse_loss_grad: NULL buffer or n < 1");
     g_prof_tag = 0;
     STGCN_LAUNCH("mse_loss_grad", (hipStream_t)stream, mse_loss_grad_kernel, dim3(1), dim3(1024), 16 * sizeof(float), pred, target, (long)n,
-                 grad_scale, loss, dpred, reinterpret_cast<const long*>(target_index_dev), (long)target_index_stride);
+                 grad_scale, loss, dpred, reinterpret_cast<const long*>(target_index_dev), (long)target_index_stride,
+                 static_cast<const long*>(nullptr), 0u);
+    return STGCN_OK;
+}
+
+int stgcn_mse_loss_grad_windows(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
+                                const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
+                                int64_t window_floats, void* stream) {
+    if (!target_window_dev) return stgcn_mse_loss_grad(pred, target, n, grad_scale, loss, dpred, target_index_dev, target_index_stride, stream);
+    STGCN_FLUSH_PENDING_PACK();
+    if (!pred || !target || !loss || !dpred || n < 1) return fail(STGCN_ERR_INVALID, "stgcn_mse_loss_grad_windows: NULL buffer or n < 1");
+    if (!target_index_dev) return fail(STGCN_ERR_INVALID, "stgcn_mse_loss_grad_windows: target_window_dev (window table) needs target_index_dev != NULL");
+    if (window_floats < 1 || n % window_floats != 0 || n >= (1ll << 31))
+        return fail(STGCN_ERR_INVALID, "stgcn_mse_loss_grad_windows: n = %lld must be a multiple of window_floats = %lld and below 2^31",
+                    (long long)n, (long long)window_floats);
+    g_prof_tag = 0;
+    STGCN_LAUNCH("mse_loss_grad", (hipStream_t)stream, mse_loss_grad_kernel, dim3(1), dim3(1024), 16 * sizeof(float), pred, target, (long)n,
+                 grad_scale, loss, dpred, reinterpret_cast<const long*>(target_index_dev), (long)target_index_stride,
+                 reinterpret_cast<const long*>(target_window_dev), (unsigned)window_floats);
     return STGCN_OK;
 }
 

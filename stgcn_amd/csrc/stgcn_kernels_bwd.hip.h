@@ -1066,7 +1066,7 @@ __global__ __launch_bounds__(256) void align_gate_bwd_kernel(AlignBwdArgs a) {
                     s = ld4(a.S + (size_t)R * c0 + 4 * c4);
                 } else {   // cheap conv (K <= 16): Z = im2col(x) @ W_eff + b_eff recomputed instead of stored
                     const unsigned per_b = (unsigned)(a.ts.Tdst * a.ts.N), Ru = (unsigned)R, b = Ru / per_b, rem = Ru - b * per_b;
-                    const float* xr = tap_base(a.ts) + ((size_t)b * tap_bstride(a.ts) + rem) * a.ts.C;
+                    const float* xr = tap_origin(a.ts) + tap_src_row(tap_win(a.ts), b, rem) * a.ts.C;
                     u = ld4(a.bias + 4 * c4);
                     f32x4 qv = ld4(a.bias + c0 + 4 * c4);
                     const int K = a.ts.taps * a.ts.C;
@@ -1177,10 +1177,13 @@ __global__ __launch_bounds__(256) void thin_tc1_bwd_kernel(ThinBwdArgs a) {
         wqr[k] = et_round4<ET>(k < K ? ld4(a.Wd + (size_t)k * NC + c0 + 4 * c4) : zero4());
     }
     const f32x4 bu = ld4(a.bias + 4 * c4), bqv = ld4(a.bias + c0 + 4 * c4);
-    const ET* const xsrc = tap_base<ET>(a.ts);
+    const ET* const xsrc = tap_origin<ET>(a.ts);
     const ET* const dA_ = et_ptr<ET>(a.dA);
     ET* const dZ_ = et_ptr<ET>(a.dZ);
-    const size_t xbs = (size_t)tap_bstride(a.ts);
+    const TapWin tw0 = tap_win(a.ts);
+    const long* const wtab = tw0.tab;   // (scalars, rebuilt into a TapWin inside the lambda: captured as a struct it stayed in scratch memory)
+    const long wrows = tw0.wrows;
+    const size_t xbs = tw0.xbs;
     // dA rows (one 16-byte load per thread) and the K valid taps of x (one scalar load for the first 64*K threads) of a tile are requested
     // together, raw, ONE TILE AHEAD (unconditional: clamped rows, masked where they are stored); the Align weights of the wave's column
     // tile are stationary.  Loaded where they are used, every tile waited for its dA / x round trip and then for the weight fragment's.
@@ -1192,7 +1195,7 @@ __global__ __launch_bounds__(256) void thin_tc1_bwd_kernel(ThinBwdArgs a) {
         da = ldraw4(dA_ + (size_t)Ra * 16 + 4 * qa);
         const unsigned Ru = (unsigned)Rx, b = Ru / per_b, rem = Ru - b * per_b;
         const int tap = kx / a.ts.C, ch = kx - tap * a.ts.C;
-        xv = ldraw1(xsrc + ((size_t)b * xbs + rem + (size_t)tap * a.ts.N) * a.ts.C + ch);
+        xv = ldraw1(xsrc + (tap_src_row(TapWin{wtab, wrows, xbs}, b, rem) + (size_t)tap * a.ts.N) * a.ts.C + ch);
     };
     PreW<1, 1> waw;
     pre_load_weights<1, 1>(waw, a.WaT, 1, wave, 4);
@@ -1369,9 +1372,9 @@ __device__ __forceinline__ void tconv_bwd_weight_body(const TconvBwdWeightArgs& 
     const int K = a.ts.taps * a.ts.C;
     const unsigned per_b = (unsigned)(a.ts.Tdst * a.ts.N);   // rows < 2^31 (checked on the host): 32-bit divisions only
     const int csh = pow2_shift(a.ts.C);
-    const ET* const xsrc = tap_base<ET>(a.ts);
+    const ET* const xsrc = tap_origin<ET>(a.ts);
     const ET* const dZ_ = et_ptr<ET>(a.dZ);
-    const size_t xbs = (size_t)tap_bstride(a.ts);
+    const TapWin tw = tap_win(a.ts);
 
     // staging registers (next step's tiles are fetched while the current step's MFMAs run)
     constexpr int NCR = (SR * (MC / 4) + kThreads - 1) / kThreads;   // float4 of the im2col tile per thread (vector path)
@@ -1394,7 +1397,7 @@ __device__ __forceinline__ void tconv_bwd_weight_body(const TconvBwdWeightArgs& 
                     if (R < crow1 && kidx < K) {
                         const unsigned Ru = (unsigned)R, b = Ru / per_b, rem = Ru - b * per_b;
                         const int tap = fast_div(kidx, a.ts.C, csh), ch = kidx - tap * a.ts.C;
-                        v = ldraw4(xsrc + ((size_t)b * xbs + rem + (size_t)tap * a.ts.N) * a.ts.C + ch);
+                        v = ldraw4(xsrc + (tap_src_row(tw, b, rem) + (size_t)tap * a.ts.N) * a.ts.C + ch);
                     }
                 }
                 creg[i] = v;
@@ -1411,7 +1414,7 @@ __device__ __forceinline__ void tconv_bwd_weight_body(const TconvBwdWeightArgs& 
                     if (R < crow1 && kidx < K) {
                         const unsigned Ru = (unsigned)R, b = Ru / per_b, rem = Ru - b * per_b;
                         const int tap = fast_div(kidx, a.ts.C, csh), ch = kidx - tap * a.ts.C;
-                        v = ldx1(xsrc + ((size_t)b * xbs + rem + (size_t)tap * a.ts.N) * a.ts.C + ch);
+                        v = ldx1(xsrc + (tap_src_row(tw, b, rem) + (size_t)tap * a.ts.N) * a.ts.C + ch);
                     }
                 }
                 cs[i] = v;

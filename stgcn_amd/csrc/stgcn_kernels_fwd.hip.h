@@ -188,11 +188,44 @@ struct TapSrc {
     long bstride;
     const long* idx_dev;
     long idx_stride;
+    // Window table (shuffled epochs; nullable): window b starts win_tab[pos + b] * idx_stride elements into the source, pos = the batch
+    // position (*idx_dev, or what the launch fused with the pack forms from it: PackSync).  bstride is ignored; the host admits the table
+    // only with idx_dev set and idx_stride a positive multiple of C below 2^31 (check_desc), so that windows start on whole source rows.
+    const long* win_tab;
 };
 // (idx_stride counts ELEMENTS of the source's storage type)
 template <typename ET = float>
 __device__ __forceinline__ const ET* tap_base(const TapSrc& ts) { return et_ptr<ET>(ts.src) + (ts.idx_dev ? *ts.idx_dev * ts.idx_stride : 0); }
 __device__ __forceinline__ long tap_bstride(const TapSrc& ts) { return ts.bstride ? ts.bstride : (long)ts.Tsrc * ts.N; }
+
+// ---- THE place where a flat output row -- window b, row rem = t * N + n of it -- becomes a source row (in units of C elements) ----
+// Every reader of a TapSrc goes through tap_src_row; both placements of the windows live here and nowhere else:
+//   strided / index mode:  b * xbs + rem                      counted from tap_base (which carries the index shift)
+//   table mode:            tab[b] * wrows + rem               counted from the source itself, tab = win_tab + pos
+// Per ROW, not per tile: a 16-row tile can straddle two windows, and with a table the two are unrelated addresses.
+struct TapWin {
+    const long* tab;   // win_tab + pos (nullptr: no table)
+    long wrows;        // source rows per table unit: idx_stride / C
+    size_t xbs;        // rows between the starts of consecutive windows (strided / index mode)
+};
+__device__ __forceinline__ TapWin tap_win_at(const TapSrc& ts, long pos) {
+    TapWin w;
+    w.tab = ts.win_tab ? ts.win_tab + pos : nullptr;
+    w.wrows = ts.win_tab ? (long)((unsigned)ts.idx_stride / (unsigned)ts.C) : 0;   // (once per thread; 32-bit: see TapSrc)
+    w.xbs = (size_t)tap_bstride(ts);
+    return w;
+}
+__device__ __forceinline__ TapWin tap_win(const TapSrc& ts) { return tap_win_at(ts, ts.win_tab ? *ts.idx_dev : 0); }
+// the pointer the rows of tap_src_row count from
+template <typename ET = float>
+__device__ __forceinline__ const ET* tap_origin(const TapSrc& ts) { return ts.win_tab ? et_ptr<ET>(ts.src) : tap_base<ET>(ts); }
+// the table word of window b: one 64-bit global load (0 without a table).  Apart from its use, so that a kernel that requests its loads a
+// tile ahead can request this word a tile before that.
+__device__ __forceinline__ long tap_win_start(const TapWin& w, unsigned b) { return w.tab ? w.tab[b] : 0; }
+__device__ __forceinline__ size_t tap_src_row(const TapWin& w, unsigned b, unsigned rem, long start) {
+    return w.tab ? (size_t)start * (size_t)w.wrows + rem : (size_t)b * w.xbs + rem;
+}
+__device__ __forceinline__ size_t tap_src_row(const TapWin& w, unsigned b, unsigned rem) { return tap_src_row(w, b, rem, tap_win_start(w, b)); }
 
 // per-tile row bookkeeping in LDS: rowbase[r] = flat source row of tap 0, rowt[r] = t (or -2^20 if the
 // row is beyond the tensor, which makes every tap invalid)
@@ -207,7 +240,8 @@ __device__ __forceinline__ void tile_rowinfo(const TapSrc& ts, long tile_row0, i
             const unsigned b = Ru / per_b;
             const unsigned rem = Ru - b * per_b;
             t = (int)(rem / (unsigned)ts.N);
-            base = (int)(b * (unsigned)tap_bstride(ts) + rem);   // = (b*Tsrc + t)*N + n for dense windows
+            base = (int)tap_src_row(tap_win(ts), b, rem);   // = (b*Tsrc + t)*N + n for dense windows; the table word of the row's window is
+                                                            // read here, once, and cached in rowbase with the rest of the row's address
         }
         rowbase[r] = base;
         rowt[r] = t;
@@ -219,7 +253,7 @@ template <int TR = kTileRows, int THREADS = kThreads, typename ET = float>
 __device__ __forceinline__ void tile_load_segment(const TapSrc& ts, const int* rowbase, const int* rowt, int k0, int kseg,
                                                   float* At, int lda) {
     const int K = ts.taps * ts.C, csh = pow2_shift(ts.C);
-    const ET* const src = tap_base<ET>(ts);
+    const ET* const src = tap_origin<ET>(ts);
     if ((ts.C & 3) == 0) {
         const int q4 = kseg >> 2, qsh = pow2_shift(q4);
         for (int idx = threadIdx.x; idx < TR * q4; idx += THREADS) {
@@ -288,7 +322,7 @@ __device__ __forceinline__ void tile_prefetch_segment(const TapSrc& ts, const in
                                                       TileRegs<TR, THREADS>& regs) {
     constexpr int NV = (TR * (kSegMax / 4) + THREADS - 1) / THREADS;
     const int K = ts.taps * ts.C, q4 = kseg >> 2, qsh = pow2_shift(q4), csh = pow2_shift(ts.C);
-    const ET* const src = tap_base<ET>(ts);
+    const ET* const src = tap_origin<ET>(ts);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int idx = threadIdx.x + i * THREADS;
@@ -605,8 +639,8 @@ template <int TR, int SB, int THREADS = kThreads, typename ET = float>
 __device__ __forceinline__ void stage_tile_fwd(const TapSrc& ts, long row0, int KP, float* At, int lda) {
     const int tid = threadIdx.x, K = ts.taps * ts.C;
     const RowCoord c0 = row_coord(ts, row0 < ts.rows ? row0 : 0);
-    const ET* const src = tap_base<ET>(ts);
-    const long bs = tap_bstride(ts);
+    const ET* const src = tap_origin<ET>(ts);
+    const TapWin tw = tap_win(ts);
     if ((ts.C & 3) == 0) {
         const int c4n = ts.C >> 2, c4sh = pow2_shift(c4n), per_tap = TR * c4n, total = ts.taps * per_tap;
         for (int base = 0; base < total; base += THREADS * SB) {
@@ -624,7 +658,7 @@ __device__ __forceinline__ void stage_tile_fwd(const TapSrc& ts, long row0, int 
                     dst[i] = r * lda + tap * ts.C + 4 * c4;
                     if (row0 + r < ts.rows) {
                         const RowCoord c = row_advance(ts, c0, r);
-                        v[i] = ldx4(src + ((size_t)c.b * bs + (size_t)(c.t + tap) * ts.N + c.n) * ts.C + 4 * c4);
+                        v[i] = ldx4(src + (tap_src_row(tw, (unsigned)c.b, (unsigned)(c.t * ts.N + c.n)) + (size_t)tap * ts.N) * ts.C + 4 * c4);
                     }
                 }
             }
@@ -655,7 +689,7 @@ __device__ __forceinline__ void stage_tile_fwd(const TapSrc& ts, long row0, int 
                     if (q < K && row0 + r < ts.rows) {
                         const int tap = q / ts.C, ch = q - tap * ts.C;
                         const RowCoord c = row_advance(ts, c0, r);
-                        v[i] = ldx1(src + ((size_t)c.b * bs + (size_t)(c.t + tap) * ts.N + c.n) * ts.C + ch);
+                        v[i] = ldx1(src + (tap_src_row(tw, (unsigned)c.b, (unsigned)(c.t * ts.N + c.n)) + (size_t)tap * ts.N) * ts.C + ch);
                     }
                 }
             }

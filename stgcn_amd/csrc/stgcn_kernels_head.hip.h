@@ -147,9 +147,22 @@ struct FcBwdArgs {
     const float* target;
     const long* target_index;   // nullable: target += *target_index * target_index_stride
     long target_index_stride;
+    // window table (nullable; needs target_index): the target_window_elems values of window b are read at
+    // target + target_window[*target_index + b] * target_index_stride  (label_ptr)
+    const long* target_window;
+    unsigned target_window_elems;
     float loss_scale;
     LnRowstatOut rs;      // row partials of the head's LayerNorm backward (dyln is its output gradient); rs.rowstat == null: off
 };
+
+// Address of label element e of a batch: index mode (tab == nullptr) y already carries the index shift; table mode, window b = e / per_w
+// reads its row at y + tab[b] * stride (tab = the table at the batch position).  The label base is offset by n_his + n_pred - 1 series rows,
+// so the table of window starts that places the inputs (TapSrc.win_tab) places the labels too.
+__device__ __forceinline__ const float* label_ptr(const float* y, const long* tab, long stride, unsigned per_w, long e) {
+    if (!tab) return y + e;
+    const unsigned eu = (unsigned)e, b = eu / per_w;   // (n < 2^31: checked on the host)
+    return y + tab[b] * stride + (eu - b * per_w);
+}
 
 template <int WM, int NT, typename ET>
 __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
@@ -165,7 +178,9 @@ __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
     float db2 = 0.f, lsum = 0.f;
     const f32x4 w2 = ld4(a.w2 + 4 * c4);
     const float* tgt = a.target;
-    if (a.pred && a.target_index) tgt += *a.target_index * a.target_index_stride;
+    const long* ttab = nullptr;
+    if (a.pred && a.target_window) ttab = a.target_window + *a.target_index;
+    else if (a.pred && a.target_index) tgt += *a.target_index * a.target_index_stride;
     const float inv_n = 1.0f / (float)a.rows;
     PreW<NT, 8> w;   // fc1 weight fragments of the whole K = c1 (8 chunks), requested before the first tile is touched
     pre_load_weights<NT, 8>(w, a.W1d, a.KCH, wave, 4);
@@ -178,7 +193,7 @@ __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
             if (R < a.rows) {
                 float go;
                 if (a.pred) {   // uniform
-                    const float df = a.pred[R] - tgt[R];
+                    const float df = a.pred[R] - *label_ptr(tgt, ttab, a.target_index_stride, a.target_window_elems, R);
                     go = 2.0f * df * inv_n * a.loss_scale;
                     if (c4 == 0) lsum += df * df;
                 } else {
@@ -358,14 +373,17 @@ __global__ __launch_bounds__(256) void optim_kernel(AdamwArgs a, OptimExtra x) {
 // order (bitwise reproducible).
 // ================================================================================================
 __global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* pred, const float* y, long n, float gscale, float* loss,
-                                                              float* dpred, const long* y_idx_dev, long y_idx_stride) {
-    if (y_idx_dev) y += *y_idx_dev * y_idx_stride;   // labels straight from the resident series (device-side windowing)
+                                                              float* dpred, const long* y_idx_dev, long y_idx_stride, const long* y_tab,
+                                                              unsigned y_per_w) {
+    const long* tab = nullptr;   // window table at the batch position (label_ptr)
+    if (y_tab) tab = y_tab + *y_idx_dev;
+    else if (y_idx_dev) y += *y_idx_dev * y_idx_stride;   // labels straight from the resident series (device-side windowing)
     extern __shared__ float stgcn_smem[];   // [16] wave sums
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float k = 2.0f * gscale / (float)n;
     float acc = 0.f;
     for (long e = tid; e < n; e += 1024) {
-        const float d = pred[e] - y[e];
+        const float d = pred[e] - *label_ptr(y, tab, y_idx_stride, y_per_w, e);
         acc += d * d;
         dpred[e] = k * d;
     }

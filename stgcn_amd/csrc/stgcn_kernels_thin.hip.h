@@ -24,10 +24,17 @@ namespace stgcn {
 
 constexpr int kThinTaps = 4;   // K = Kt * c_in <= 4
 
-// the (b, t, n) decomposition of a flat output row and the source row of its tap 0 (in units of source ROWS of C elements)
-__device__ __forceinline__ size_t thin_row_base(const TapSrc& ts, long R, unsigned per_b, size_t xbs) {
+// the (b, t, n) decomposition of a flat output row and the source row of its tap 0 (in units of source ROWS of C elements; tap_src_row);
+// `start`: the table word of the row's window (thin_row_start), requested by the caller one tile before the row's own loads
+__device__ __forceinline__ size_t thin_row_base(const TapWin& tw, long R, unsigned per_b, long start) {
     const unsigned Ru = (unsigned)R, b = Ru / per_b, rem = Ru - b * per_b;
-    return (size_t)b * xbs + rem;
+    return tap_src_row(tw, b, rem, start);
+}
+// the table word of lane l15's row of tile t (clamped like the row's loads; 0 without a table)
+__device__ __forceinline__ long thin_row_start(const TapWin& tw, long t, long tiles, long rows, int l15, unsigned per_b) {
+    if (!tw.tab) return 0;   // (uniform)
+    const long R0 = (t < tiles ? t : tiles - 1) * 16 + l15, R = R0 < rows ? R0 : rows - 1;
+    return tap_win_start(tw, (unsigned)R / per_b);
 }
 
 // W_eff[k][o] of the thin layer from the reference's own parameter (what pack_kernel's PK_TCONV_DENSE writes, tconv_weff with C < 64: the
@@ -125,7 +132,6 @@ __device__ __forceinline__ void thin_tc1_fwd_body(const ThinFwdArgs& a, const in
     const long rows = a.ts.rows, tiles = (rows + 15) >> 4;
     const int K = a.ts.taps * a.ts.C, C = a.ts.C, N = a.ts.N;
     const unsigned per_b = (unsigned)(a.ts.Tdst * N);
-    const size_t xbs = (size_t)tap_bstride(a.ts);
     ET* const A_ = et_ptr<ET>(a.A);
 
     ThinConv<ET> cw;
@@ -150,18 +156,21 @@ __device__ __forceinline__ void thin_tc1_fwd_body(const ThinFwdArgs& a, const in
 
     // (the operand loads above are in flight while the index arrives: one wait covers both)
     const bool shared_idx = sy.on && a.ts.idx_dev == sy.idx_ptr;   // (uniform)
-    const ET* xsrc = shared_idx ? et_ptr<ET>(a.ts.src) : tap_base<ET>(a.ts);
+    const ET* xsrc = shared_idx ? et_ptr<ET>(a.ts.src) : tap_origin<ET>(a.ts);
+    TapWin tw = shared_idx ? tap_win_at(a.ts, 0) : tap_win(a.ts);
     if (shared_idx) {   // the window index is bumped by the pack role of THIS launch: see PackSync
         const long old = (long)chain_ld64(reinterpret_cast<const unsigned long long*>(a.ts.idx_dev));
         chain_drain_stores();                       // (s_waitcnt vmcnt(0): the index has arrived before this wave reports in)
         if (lane == 0) chain_add(g_pack_readers + (int)(wave_id & (kPackSyncWords - 1)) * kPackSyncStride, 1u);
-        const long v = old + sy.inc;
-        xsrc = et_ptr<ET>(a.ts.src) + (sy.mod > 0 ? v % sy.mod : v) * a.ts.idx_stride;
+        const long v = old + sy.inc, pos = sy.mod > 0 ? v % sy.mod : v;
+        if (a.ts.win_tab) tw = tap_win_at(a.ts, pos);           // (uniform) table mode: the position selects table rows, not source rows
+        else xsrc = et_ptr<ET>(a.ts.src) + pos * a.ts.idx_stride;
     }
-    // the K taps of row (tile, l15): scalar loads, raw, requested one tile ahead
-    auto request = [&](long t, Raw1<ET> (&xr)[kThinTaps]) __attribute__((always_inline)) {
+    // the K taps of row (tile, l15): scalar loads, raw, requested one tile ahead; with a window table the row's table word (`start`) must be
+    // there before they can be addressed, so IT is requested two tiles ahead (ws0 / ws1 below) and has arrived with the previous tile's taps
+    auto request = [&](long t, long start, Raw1<ET> (&xr)[kThinTaps]) __attribute__((always_inline)) {
         const long R0 = (t < tiles ? t : tiles - 1) * 16 + l15, R = R0 < rows ? R0 : rows - 1;
-        const size_t base = thin_row_base(a.ts, R, per_b, xbs);
+        const size_t base = thin_row_base(tw, R, per_b, start);
 #pragma unroll
         for (int k = 0; k < kThinTaps; ++k) {
             const int kk = k < K ? k : K - 1, tap = kk / C, ch = kk - tap * C;
@@ -169,12 +178,16 @@ __device__ __forceinline__ void thin_tc1_fwd_body(const ThinFwdArgs& a, const in
         }
     };
     Raw1<ET> xn[kThinTaps];
-    request(wave_id, xn);
+    const long ws0 = thin_row_start(tw, wave_id, tiles, rows, l15, per_b);
+    long ws1 = thin_row_start(tw, wave_id + nwaves, tiles, rows, l15, per_b);
+    request(wave_id, ws0, xn);
     for (long t = wave_id; t < tiles; t += nwaves) {
         f32x4 xk;
 #pragma unroll
         for (int k = 0; k < kThinTaps; ++k) xk[k] = k < K ? cvt1(xn[k]) : 0.f;
-        request(t + nwaves, xn);   // (past the last tile: a valid address, never used)
+        const long ws2 = thin_row_start(tw, t + 2 * nwaves, tiles, rows, l15, per_b);   // (issued ahead of the taps: in-order returns)
+        request(t + nwaves, ws1, xn);   // (past the last tile: a valid address, never used)
+        ws1 = ws2;
         f32x4 acc[8];
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) acc[mt] = bz[mt];
@@ -243,8 +256,8 @@ __device__ __forceinline__ void thin_tc1_bwd2_body(const ARGS& a) {
     const long rows = a.rows, tiles = (rows + 15) >> 4;
     const int K = a.ts.taps * a.ts.C, C = a.ts.C, N = a.ts.N;
     const unsigned per_b = (unsigned)(a.ts.Tdst * N);
-    const size_t xbs = (size_t)tap_bstride(a.ts);
-    const ST* const xsrc = tap_base<ST>(a.ts);
+    const TapWin tw = tap_win(a.ts);
+    const ST* const xsrc = tap_origin<ST>(a.ts);
     const ST* const dA_ = et_ptr<ST>(a.dA);
     ST* const dZ_ = et_ptr<ST>(a.dZ);
 
@@ -269,10 +282,10 @@ __device__ __forceinline__ void thin_tc1_bwd2_body(const ARGS& a) {
     for (int i = 0; i < 4; ++i) accA[i] = zero4();
 
     struct Req { Raw4<ST> da; Raw1<ST> x[kThinTaps]; };
-    auto request = [&](long t, Req& q) __attribute__((always_inline)) {
+    auto request = [&](long t, long start, Req& q) __attribute__((always_inline)) {   // (start: as in thin_tc1_fwd_body)
         const long R0 = (t < tiles ? t : tiles - 1) * 16 + l15, R = R0 < rows ? R0 : rows - 1;
         q.da = ldraw4(dA_ + (size_t)R * 16 + 4 * g);
-        const size_t base = thin_row_base(a.ts, R, per_b, xbs);
+        const size_t base = thin_row_base(tw, R, per_b, start);
 #pragma unroll
         for (int k = 0; k < kThinTaps; ++k) {
             const int kk = k < K ? k : K - 1, tap = kk / C, ch = kk - tap * C;
@@ -280,7 +293,9 @@ __device__ __forceinline__ void thin_tc1_bwd2_body(const ARGS& a) {
         }
     };
     Req rq;
-    request(wave_id, rq);
+    const long ws0 = thin_row_start(tw, wave_id, tiles, rows, l15, per_b);
+    long ws1 = thin_row_start(tw, wave_id + nwaves, tiles, rows, l15, per_b);
+    request(wave_id, ws0, rq);
     for (long t = wave_id; t < tiles; t += nwaves) {
         const long R = t * 16 + l15;
         const bool rv = R < rows;
@@ -288,7 +303,9 @@ __device__ __forceinline__ void thin_tc1_bwd2_body(const ARGS& a) {
         f32x4 xk;
 #pragma unroll
         for (int k = 0; k < kThinTaps; ++k) xk[k] = k < K ? cvt1(rq.x[k]) : 0.f;
-        request(t + nwaves, rq);
+        const long ws2 = thin_row_start(tw, t + 2 * nwaves, tiles, rows, l15, per_b);
+        request(t + nwaves, ws1, rq);
+        ws1 = ws2;
         dba += da;
         // tiles the row contractions read transposed: dA[row][j], x[row][k] (+ the column of ones)
         st4(Dt + l15 * kThinLdD + 4 * g, da);

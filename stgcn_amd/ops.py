@@ -58,16 +58,24 @@ def _check_device(t: torch.Tensor, what: str, activation: bool = False):
         raise RuntimeError(f"{what}: stgcn_amd runs on MI355X only (tensor is on {t.device}); there is no CPU fallback")
 
 
-_input_index: Dict[int, Tuple[torch.Tensor, int]] = {}
+_input_index: Dict[int, Tuple[torch.Tensor, int, Optional[torch.Tensor]]] = {}
 
 
-def bind_input_index(base: torch.Tensor, index: torch.Tensor, stride_floats: int) -> None:
+def bind_input_index(base: torch.Tensor, index: torch.Tensor, stride_floats: int, table: Optional[torch.Tensor] = None) -> None:
     """Device-side batch position: from now on a fused-operator input (or an MSE target) whose storage starts at
     ``base.data_ptr()`` is read ``index[0] * stride_floats`` floats further on, with ``index`` an int64 DEVICE scalar that a
     captured training step advances by itself (``stgcn_prepack`` counters).  Kernel arguments are frozen inside a hipGraph;
-    this is how the replayed step walks through a resident series without per-step input copies."""
+    this is how the replayed step walks through a resident series without per-step input copies.
+
+    ``table`` (int64 device tensor of window starts; shuffled epochs): window ``b`` of the batch is read
+    ``table[index[0] + b] * stride_floats`` floats into ``base`` instead -- the position selects a run of table entries, not a run of
+    consecutive windows (``x_window_dev`` / ``target_window_dev``).  The binding keeps the table alive; the caller keeps
+    ``index[0] + B`` within it and its entries inside the storage behind ``base``."""
     assert index.dtype == torch.int64 and index.numel() == 1 and index.device == base.device
-    _input_index[base.data_ptr()] = (index, int(stride_floats))
+    if table is not None:
+        if table.dtype != torch.int64 or table.dim() != 1 or not table.is_contiguous() or table.device != base.device:
+            raise ValueError("bind_input_index: table must be a contiguous 1-D int64 tensor on the device of base")
+    _input_index[base.data_ptr()] = (index, int(stride_floats), table)
 
 
 def unbind_input_index(base: torch.Tensor) -> None:
@@ -75,8 +83,9 @@ def unbind_input_index(base: torch.Tensor) -> None:
 
 
 def _index_of(t: torch.Tensor):
+    """(index pointer, stride in floats, window-table pointer) bound to ``t``'s storage start; (None, 0, None) without a binding."""
     e = _input_index.get(t.data_ptr())
-    return (None, 0) if e is None else (e[0].data_ptr(), e[1])
+    return (None, 0, None) if e is None else (e[0].data_ptr(), e[1], None if e[2] is None else e[2].data_ptr())
 
 
 def window_strided_rows(x_p: torch.Tensor) -> Optional[int]:
@@ -92,7 +101,8 @@ def window_strided_rows(x_p: torch.Tensor) -> Optional[int]:
 
 
 def make_desc(cfg: BlockConfig, B: int, T: int, training: bool, need_dx: bool, prepacked: bool = False, defer: bool = False,
-              x_bstride: int = 0, x_index: Optional[int] = None, x_index_stride: int = 0, dtype: torch.dtype = torch.float32) -> StblockDesc:
+              x_bstride: int = 0, x_index: Optional[int] = None, x_index_stride: int = 0, dtype: torch.dtype = torch.float32,
+              x_window: Optional[int] = None) -> StblockDesc:
     if cfg.act_func not in _lib.ACT:
         raise NotImplementedError(f"ERROR: The activation function {cfg.act_func} is not implemented.")  # layers.py:117-118
     if cfg.graph_conv_type not in _lib.GRAPH_CONV:
@@ -111,6 +121,7 @@ def make_desc(cfg: BlockConfig, B: int, T: int, training: bool, need_dx: bool, p
     d.prepacked = 1 if prepacked else 0
     d.defer_reduce = 1 if defer else 0
     d.x_bstride, d.x_index_dev, d.x_index_stride = int(x_bstride), x_index, int(x_index_stride)
+    d.x_window_dev = x_window
     d.dtype = ACT_DTYPES[dtype]
     return d
 
@@ -277,7 +288,12 @@ def mse_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, grad_scale: floa
         raise ValueError(f"mse_loss_and_grad: contiguous float32 tensors of one shape expected, got {tuple(p.shape)} / {tuple(target.shape)}")
     loss = torch.empty(1, dtype=torch.float32, device=p.device)
     dpred = torch.empty_like(p)
-    ti, tis = _index_of(target)
+    ti, tis, tw = _index_of(target)
+    if tw is not None:      # window table: one window = one row of the leading dimension
+        L.check(L.dll.stgcn_mse_loss_grad_windows(p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(),
+                                                  dpred.data_ptr(), ti, tis, tw, p.numel() // p.shape[0], _stream_of(p)),
+                "stgcn_mse_loss_grad_windows")
+        return loss, dpred
     L.check(L.dll.stgcn_mse_loss_grad(p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(), dpred.data_ptr(),
                                       ti, tis, _stream_of(p)), "stgcn_mse_loss_grad")
     return loss, dpred
@@ -340,7 +356,7 @@ def eval_metrics(words) -> dict:
 class _PendingLoss:
     """MSE loss waiting to be formed inside the head's backward (``stgcn_outblock_backward_loss``): ``mse_backward`` posts it, the
     ``_OutBlockFn.backward`` that receives the placeholder gradient takes it."""
-    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "grad_scale", "loss")
+    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "window", "grad_scale", "loss")
 
 
 _pending_loss: Optional[_PendingLoss] = None
@@ -374,7 +390,7 @@ def mse_backward(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1
     pl = _PendingLoss()
     pl.placeholder = torch.empty_like(p)            # never written, never read: its address identifies the request
     pl.pred, pl.target, pl.grad_scale = p, target, float(grad_scale)
-    pl.index, pl.index_stride = _index_of(target)
+    pl.index, pl.index_stride, pl.window = _index_of(target)
     pl.loss = torch.empty(1, dtype=torch.float32, device=p.device)
     _pending_loss = pl
     try:
@@ -579,9 +595,9 @@ class _STBlockFn(torch.autograd.Function):
         need_dx = bool(x_cl.requires_grad)
         bstride = 0 if x_cl.is_contiguous() else window_strided_rows(x_cl)
         assert bstride is not None and not (bstride and need_dx), "st_conv_block hands over dense or window-strided inputs only"
-        xi, xis = _index_of(x_cl)
+        xi, xis, xw = _index_of(x_cl)
         desc = make_desc(cfg, B, T, training, need_dx, prepacked=wsc.take_prepacked(), x_bstride=bstride, x_index=xi, x_index_stride=xis,
-                         dtype=x_cl.dtype)
+                         dtype=x_cl.dtype, x_window=xw)
         plan = query_plan(desc)
         dev = x_cl.device
         ps = [None if p is None else p.detach() for p in params]
@@ -610,7 +626,7 @@ class _STBlockFn(torch.autograd.Function):
         ctx.cfg, ctx.training, ctx.seed, ctx.offset, ctx.wsc, ctx.ws = cfg, training, seed, offset, wsc, ws
         ctx.offset_dev = offset_dev
         ctx.need_dx = need_dx
-        ctx.x_window = (bstride, xi, xis)
+        ctx.x_window = (bstride, xi, xis, xw)
         ctx.param_needs_grad = [p is not None and p.requires_grad for p in params]
         return y
 
@@ -624,7 +640,7 @@ class _STBlockFn(torch.autograd.Function):
         B, T, N, c_in = x_cl.shape
         sink = _sink
         desc = make_desc(cfg, B, T, ctx.training, ctx.need_dx, defer=sink is not None, x_bstride=ctx.x_window[0], x_index=ctx.x_window[1],
-                         x_index_stride=ctx.x_window[2], dtype=x_cl.dtype)
+                         x_index_stride=ctx.x_window[2], dtype=x_cl.dtype, x_window=ctx.x_window[3])
         dy = dy.contiguous()
         if dy.dtype != x_cl.dtype:
             dy = dy.to(x_cl.dtype)
@@ -855,6 +871,7 @@ class _OutBlockFn(torch.autograd.Function):
             hl = _lib.HeadLoss()
             hl.pred, hl.target = fused_loss.pred.data_ptr(), fused_loss.target.data_ptr()
             hl.target_index_dev, hl.target_index_stride, hl.grad_scale = fused_loss.index, fused_loss.index_stride, fused_loss.grad_scale
+            hl.target_window_dev = fused_loss.window
             ctx.keep_loss = fused_loss                  # the buffers outlive a deferred reduction
             L.check(L.dll.stgcn_outblock_backward_loss(C.byref(desc), C.byref(pst), x_cl.data_ptr(), C.byref(hl), saved.data_ptr(),
                                                        ctx.ws.data_ptr(), C.byref(gst), None if dx is None else dx.data_ptr(),

@@ -380,6 +380,46 @@ def chained_fwd_bwd(model, x, y, chains: int, streams=None):
     return total
 
 
+class WindowOrder:
+    """The window table of a shuffled epoch: ``order`` is a static int64 device tensor of ``usable`` window starts (the windows in whole
+    global minibatches); the step at position ``pos`` reads window ``b`` from series row ``order[pos + b]`` (``ops.bind_input_index(...,
+    table=order)``).  The buffer is allocated once and only ever written in place: a captured graph holds its address."""
+
+    def __init__(self, num: int, usable: int, device, seed: int = 0):
+        self.num, self.usable = int(num), int(usable)
+        assert 0 < self.usable <= self.num
+        self.order = torch.arange(self.usable, dtype=torch.int64, device=device)      # identity: the unshuffled epoch
+        # a CPU generator: every data-parallel rank with the same seed draws the same table, no collective needed
+        self.generator = torch.Generator(device="cpu")
+        self.generator.manual_seed(int(seed))
+
+    def set_order(self, starts) -> None:
+        """``starts``: ``usable`` int64 window starts (sequence or tensor), each in [0, num - 1].  Checked on the host BEFORE anything
+        is uploaded (ValueError); then written into the existing buffer on the current stream."""
+        import numpy as np
+        if isinstance(starts, torch.Tensor):
+            if starts.dtype != torch.int64:
+                raise ValueError(f"set_order: int64 window starts expected, got {starts.dtype}")
+            host = starts.detach().to("cpu").reshape(-1) if starts.dim() == 1 else None
+        else:
+            arr = np.asarray(starts)
+            if arr.dtype != np.int64:
+                raise ValueError(f"set_order: int64 window starts expected, got {arr.dtype}")
+            host = torch.from_numpy(np.ascontiguousarray(arr)) if arr.ndim == 1 else None
+        if host is None or host.numel() != self.usable:
+            raise ValueError(f"set_order: {self.usable} window starts expected (one per window of the whole global minibatches), got "
+                             f"{'a non 1-D value' if host is None else host.numel()}")
+        lo, hi = int(host.min()), int(host.max())
+        if lo < 0 or hi > self.num - 1:
+            raise ValueError(f"set_order: window starts must lie in [0, {self.num - 1}], got [{lo}, {hi}]")
+        self.order.copy_(host, non_blocking=False)
+
+    def reshuffle(self) -> None:
+        """The next epoch's permutation: a draw over ALL ``num`` windows cut to whole minibatches, so that a different remainder is left
+        out every epoch (``DataLoader(shuffle=True, drop_last=True)``)."""
+        self.set_order(torch.randperm(self.num, generator=self.generator)[:self.usable])
+
+
 class GraphedTrainStep:
     """The loop body of main.py:165-169 captured once into hipGraph(s) and replayed.
 
@@ -396,13 +436,20 @@ class GraphedTrainStep:
 
     def __init__(self, model, optimizer, x_example: torch.Tensor, y_example: torch.Tensor, world: int = 1, warmup: int = 3,
                  chains: int = 1, fused: Optional[bool] = None, series: Optional[torch.Tensor] = None, n_his: int = 12,
-                 n_pred: int = 3, rank: int = 0, capture_collective: bool = False):
+                 n_pred: int = 3, rank: int = 0, capture_collective: bool = False, shuffle: bool = False, shuffle_seed: int = 0):
         """``series``: optional resident (time, N) float32 device tensor (already z-scored).  The step then takes its windows
         straight from it (device-side windowing): window b of the minibatch is rows
         [s + b, s + b + n_his) of the series (read in place through a strided view, no (num, 1, n_his, N) tensor, no per-step
         input copies), its label row s + b + n_his + n_pred - 1 (script/dataloader.py:32-47), and s advances by the global
         batch on the device every replay (unshuffled order like main.py:127, wrapping at the end of the series).  Call the
         step without arguments; ``x_example`` / ``y_example`` only give the batch size.
+
+        ``shuffle`` (with ``series``): shuffled epochs.  The step reads window b from series row ``order[s + b]`` of a device table
+        (``step.order``, int64, one entry per window of the whole global minibatches) instead of row ``s + b``; ``s`` still advances by
+        the global batch on the device, rank r still reads entries ``s + r B + b``.  The first permutation is drawn before the warm-up
+        steps (``torch.randperm`` over ALL windows with a CPU generator seeded ``shuffle_seed``, cut to whole minibatches: every rank
+        draws the same table); ``reshuffle()`` draws the next one, ``set_order(starts)`` installs any table.  Both write the existing
+        buffer in place: no re-capture, no per-step copies, the same launches.  Without ``shuffle`` no table is bound.
 
         ``capture_collective`` (world > 1): record the gradient all-reduce INSIDE the graph -- one graph per step (forward, backward,
         reductions, RCCL all-reduce, AdamW), no host round trip around the collective.  Only for a backend whose collectives are stream
@@ -413,6 +460,9 @@ class GraphedTrainStep:
         self.model, self.opt, self.world = model, optimizer, world
         dev = x_example.device
         self.series, self.index, self._index_bump = series, None, None
+        self._order: Optional[WindowOrder] = None
+        if shuffle and series is None:
+            raise ValueError("shuffle=True needs the resident series (series=...)")
         self.chains = int(chains)                 # micro-batch chains on concurrent streams (chained_fwd_bwd)
         if fused is None:
             fused = os.environ.get("STGCN_FUSED_STEP", "1") != "0"
@@ -444,8 +494,12 @@ class GraphedTrainStep:
             self.y = series[n_his + n_pred - 1:n_his + n_pred - 1 + B]                         # label rows, (B, N) contiguous
             self.index = torch.full((1,), rank * B, dtype=torch.int64, device=dev)             # first window of this rank
             self._index_bump = (self.index, B * world, usable)
-            ops.bind_input_index(self.x, self.index, N)
-            ops.bind_input_index(self.y, self.index, N)
+            if shuffle:
+                self._order = WindowOrder(num, usable, dev, shuffle_seed)
+                self._order.reshuffle()
+            table = None if self._order is None else self._order.order
+            ops.bind_input_index(self.x, self.index, N, table=table)
+            ops.bind_input_index(self.y, self.index, N, table=table)
         if DropoutStream.counter is None or DropoutStream.counter.device != dev:
             DropoutStream.use_device_counter(dev)
         self.counter = DropoutStream.counter     # the captured kernels hold this address: keep it alive with the graph
@@ -526,6 +580,23 @@ class GraphedTrainStep:
         # still fall back to eager launches of the same kernels), not inside a timed loop
         self(x_example, y_example)
         torch.cuda.synchronize(dev)
+
+    @property
+    def order(self) -> Optional[torch.Tensor]:
+        """The static device table of window starts (int64, one per window of the whole global minibatches); None without ``shuffle``."""
+        return None if self._order is None else self._order.order
+
+    def set_order(self, starts) -> None:
+        """Install a table of window starts (``WindowOrder.set_order``: validated on the host, written in place on the current stream)."""
+        if self._order is None:
+            raise RuntimeError("set_order: this step was built without shuffle=True (no window table is bound)")
+        self._order.set_order(starts)
+
+    def reshuffle(self) -> None:
+        """Draw the next epoch's permutation (``WindowOrder.reshuffle``); call it between epochs."""
+        if self._order is None:
+            raise RuntimeError("reshuffle: this step was built without shuffle=True (no window table is bound)")
+        self._order.reshuffle()
 
     def check(self) -> None:
         """``check_in_launch_waits`` on the step's model (synchronises: for the places where the loss is read)."""

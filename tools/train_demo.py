@@ -3,7 +3,8 @@
 (34 272 rows x 207 sensors, v = clip(55 + 10 sin(2 pi t / 288 + phi_n) + N(0, 3^2), 0, 80); the real
 vel.csv is not available offline): 70/15/15 split (main.py:108-114), z-score fitted on the training rows (main.py:116-119),
 12 -> n_pred windows (script/dataloader.py:32-47), STGCNChebGraphConv on the real METR-LA operator, MSE + AdamW (or --opt nadamw | lion)(1e-3, 1e-3)
-with StepLR(10, 0.95) per epoch (main.py:147-156), unshuffled minibatches of 32 (main.py:126-131), validation loss per epoch
+with StepLR(10, 0.95) per epoch (main.py:147-156), unshuffled minibatches of 32 (main.py:126-131; --shuffle: a fresh permutation of the
+windows every epoch, drawn on the host and read through the step's device table), validation loss per epoch
 (script/utility.py:90-101), test MAE / RMSE / WMAPE at the end (script/utility.py:103-121).
 
 The training loop is `GraphedTrainStep(series=...)`: the z-scored (time, N) training series stays resident on the GPU and the
@@ -12,7 +13,7 @@ replayed every epoch): the metrics are summed on the device, `eval_s` beside `ep
 One JSON line per epoch and one for the test metrics; a persistence forecast
 (y_hat = last observed value) on the same windows is printed beside them for scale.
 
-  python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion]
+  python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion] [--shuffle]
 """
 import argparse
 import json
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--n-pred", type=int, default=3)
     ap.add_argument("--rows", type=int, default=34272)
     ap.add_argument("--opt", choices=("adamw", "nadamw", "lion"), default="adamw")     # main.py:59
+    ap.add_argument("--shuffle", action="store_true", help="shuffled epochs: step.reshuffle() once per epoch")
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
@@ -74,9 +76,15 @@ def main():
     val_pass = GraphedEvalPass(model, val, N_HIS, a.n_pred, BS)
     test_pass = GraphedEvalPass(model, test, N_HIS, a.n_pred, BS, scaler=zs)
     model.train()
-    step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred)
+    step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred, shuffle=a.shuffle, shuffle_seed=42)
     windows = series.shape[0] - N_HIS - a.n_pred + 1
     steps_per_epoch = windows // BS
+    first_epoch_steps = steps_per_epoch
+    if a.shuffle:
+        # one epoch = one walk through the table, so that reshuffle() falls on the wrap of the position: the constructor's own steps
+        # already took the head of the first permutation, the first epoch runs what is left of it
+        steps_per_epoch = step.order.numel() // BS
+        first_epoch_steps = steps_per_epoch - (int(step.index.item()) // BS + 1)
     test_s = data.WindowSampler(test, N_HIS, a.n_pred, dev)
 
     for epoch in range(a.epochs):
@@ -84,19 +92,22 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         acc = torch.zeros((), device=dev)
-        for _ in range(steps_per_epoch):
+        n_steps = first_epoch_steps if epoch == 0 else steps_per_epoch
+        for _ in range(n_steps):
             acc += step()                       # loss stays on the device: no per-step host sync (main.py:170 does .item())
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         step.check()                            # (once per epoch, where the loss is read: names the operator if an in-launch wait gave up)
         sched.step()
+        if a.shuffle:
+            step.reshuffle()                    # the next epoch's permutation, written into the table the graph already reads
         opt.sync_lr()                           # the captured AdamW reads its learning rate from device memory
         t0 = time.perf_counter()
         val_loss = val_pass.run()["mse"]        # one synchronise per pass (script/utility.py:90-101 on the device)
         eval_s = time.perf_counter() - t0
-        print(json.dumps({"epoch": epoch + 1, "train_loss": round(float(acc.item()) / steps_per_epoch, 6), "val_loss": round(val_loss, 6),
-                          "lr": opt.param_groups[0]["lr"], "steps": steps_per_epoch, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
-                          "train_windows_per_s": round(steps_per_epoch * BS / el, 1)}), flush=True)
+        print(json.dumps({"epoch": epoch + 1, "train_loss": round(float(acc.item()) / n_steps, 6), "val_loss": round(val_loss, 6),
+                          "lr": opt.param_groups[0]["lr"], "steps": n_steps, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
+                          "train_windows_per_s": round(n_steps * BS / el, 1)}), flush=True)
 
     m = test_pass.run()
     mae, rmse, wmape = m["mae"], m["rmse"], m["wmape"]
