@@ -792,7 +792,8 @@ _head_plan_cache: Dict[tuple, OutblockPlan] = {}
 
 
 def query_head_plan(desc: OutblockDesc) -> OutblockPlan:
-    key = tuple(getattr(desc, f) for f, _ in OutblockDesc._fields_)
+    # (STGCN_HEAD_FC_TILE: the library reads it on every call and the size of the partial arena follows the tile height)
+    key = tuple(getattr(desc, f) for f, _ in OutblockDesc._fields_) + (os.environ.get("STGCN_HEAD_FC_TILE"),)
     p = _head_plan_cache.get(key)
     if p is None:
         L = _lib.lib()

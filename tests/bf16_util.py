@@ -237,8 +237,11 @@ def assert_bf16_errors(stored, f32):
     assert not bad, f"out of tolerance: {bad}\nstored: {stored}\nf32: {f32}"
 
 
-def run_head_case_bf16(dev, N, B, c_in=64, channels=(128, 128), Ko=4, act="glu", training=True, seed=5, offset=9, pdrop=0.5):
-    """The output head with bf16 activations against outblock_fwd / outblock_bwd of the stage oracle (q = QuantBf16)."""
+def run_head_case_bf16(dev, N, B, c_in=64, channels=(128, 128), Ko=4, act="glu", training=True, seed=5, offset=9, pdrop=0.5, T=None, need_dx=True):
+    """The output head with bf16 activations against outblock_fwd / outblock_bwd of the stage oracle (q = QuantBf16).
+    T: length of the input's time axis (None: Ko, one output step); need_dx = False: x does not require grad, no input gradient is formed."""
+    T = Ko if T is None else T
+    T1 = T - Ko + 1
     from oracle import stgcn_oracle as orc
     cfg = orc.OracleConfig(Kt=3, Ks=3, n_his=12, act_func=act, graph_conv_type="cheb_graph_conv", droprate=pdrop,
                            blocks=[[1], [64, 16, 64], [64, 16, c_in], list(channels), [1]])
@@ -248,13 +251,13 @@ def run_head_case_bf16(dev, N, B, c_in=64, channels=(128, 128), Ko=4, act="glu",
              "tc1_ln.weight", "tc1_ln.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
     params = [p["output." + n].clone().to(dev).requires_grad_(True) for n in names]
     rs = np.random.RandomState(4)
-    x_np = Q(rs.standard_normal((B, c_in, Ko, N)))
-    dout_np = rs.standard_normal((B, 1, 1, N)).astype(np.float32)
+    x_np = Q(rs.standard_normal((B, c_in, T, N)))
+    dout_np = rs.standard_normal((B, 1, T1, N)).astype(np.float32)
     hcfg = ops.HeadConfig(Ko=Ko, n_vertex=N, c_in=c_in, channels=tuple(channels), end_channel=1, act_func=act, droprate=pdrop)
-    x = bf16_tensor(x_np, dev).requires_grad_(True)
+    x = bf16_tensor(x_np, dev).requires_grad_(bool(need_dx))
     wsc = ops.WorkspaceCache()
     out = ops.output_block(x, hcfg, params, training, seed, offset, wsc)
-    assert out.dtype == torch.float32 and out.shape == (B, 1, 1, N)
+    assert out.dtype == torch.float32 and out.shape == (B, 1, T1, N)
     out.backward(torch.from_numpy(dout_np).to(dev))
     if str(dev).startswith("cuda"):
         torch.cuda.synchronize()
@@ -262,14 +265,16 @@ def run_head_case_bf16(dev, N, B, c_in=64, channels=(128, 128), Ko=4, act="glu",
     keep = None
     c0, c1 = channels
     if training:
-        ks = ops.dropout_mask(B * N * c1, pdrop, seed, offset, dev).cpu().numpy().reshape(B, 1, N, c1)
+        ks = ops.dropout_mask(B * T1 * N * c1, pdrop, seed, offset, dev).cpu().numpy().reshape(B, T1, N, c1)
         keep = (ks > 0).astype(np.float64)
     hp = st.head_params_np(p, np.float64)
     out_ref, sv = st.outblock_fwd(cl(x_np), hp, Ko, c_in, channels, act, keep, pdrop, q=Q)
-    dx_ref, g_ref = st.outblock_bwd(dout_np[:, 0].astype(np.float64), sv, hp, Ko, c_in, channels, act, pdrop, True, q=Q)
+    dx_ref, g_ref = st.outblock_bwd(dout_np[:, 0].astype(np.float64), sv, hp, Ko, c_in, channels, act, pdrop, bool(need_dx), q=Q)
     rel = lambda got, ref: float(np.abs(got - ref).max() / max(1e-30, np.abs(ref).max()))
-    stored = {"head.dx": err_stored(cl(bf16_numpy(x.grad)), dx_ref)}
+    stored = {"head.dx": err_stored(cl(bf16_numpy(x.grad)), dx_ref)} if need_dx else {}
     f32 = {"head.out": rel(out.detach().cpu().numpy()[:, 0].astype(np.float64), out_ref)}
+    if not need_dx:
+        f32["grad_none_ok.head.dx"] = 0.0 if x.grad is None else 1.0
     keys = ["tc_w", "tc_b", "tc_aw", "tc_ab", "ln_w", "ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b"]
     for k, prm in zip(keys, params):
         ref = g_ref[k]

@@ -1,5 +1,9 @@
 """Fused output head (OutputBlock) on the CPU emulator vs the autograd oracle (float64), with the library's
-own dropout mask."""
+own dropout mask.
+
+The second half runs the stage-level case table of tests/test_gpu_head.py (tests/head_util.py) on the emulator: rows a-j, o, p and q.  Dropped
+from the CPU run only, for their time on the emulator: k (9 s), l (18 s), m (13 s) -- left to the GPU for the sake of the suite's total --
+and n (33 000 rows: 280 s); bf16 l and n likewise (6 s / 84 s).  The GPU run keeps the full table."""
 import numpy as np
 import pytest
 import torch
@@ -115,3 +119,61 @@ def head_wait_give_up_case(dev):
 def test_head_forward_wait_give_up_is_loud_and_not_sticky_across_launches():
     bind_emulator()
     head_wait_give_up_case("cpu")
+
+
+# ---- the stage-level case table of tests/test_gpu_head.py on the emulator (tests/head_util.py): rows a-j, o, p, q -- every row small enough
+EMU_ROWS = list("abcdefghij") + ["o", "p", "q"]
+
+
+def test_head_plan_follows_the_fc_tile_knob(monkeypatch):
+    """The workspace of a head is sized by ops.query_head_plan, which caches; the library sizes the fc partial arena by the tile height it
+    reads from STGCN_HEAD_FC_TILE on every call.  A plan cached under 32-row tiles and reused under 16-row tiles is 128 floats short for
+    this head (3 workgroups instead of 2), and the backward wrote past the workspace (found by running row a after
+    test_head_tile_height_variants in one process)."""
+    bind_emulator()
+    hcfg = ops.HeadConfig(Ko=4, n_vertex=21, c_in=64, channels=(128, 128), end_channel=1, act_func="glu", droprate=0.5)
+    monkeypatch.setenv("STGCN_HEAD_FC_TILE", "32")
+    p32 = ops.query_head_plan(ops.make_head_desc(hcfg, 2, 4, True, True))
+    monkeypatch.delenv("STGCN_HEAD_FC_TILE")
+    p16 = ops.query_head_plan(ops.make_head_desc(hcfg, 2, 4, True, True))
+    assert p16.part_floats == p32.part_floats + 128 and p16.ws_floats == p32.ws_floats + 128
+
+
+def _table_case(name, **kw):
+    from tests.head_util import assert_head_errors
+    from tests.test_gpu_head import run
+    assert_head_errors(run(name, dev="cpu", **kw))
+
+
+@pytest.mark.parametrize("name", EMU_ROWS)
+def test_head_stage_table(name):
+    _table_case(name)
+
+
+@pytest.mark.parametrize("name", ["a", "h"])
+def test_head_stage_table_fc_tile_32(name, monkeypatch):
+    monkeypatch.setenv("STGCN_HEAD_FC_TILE", "32")
+    _table_case(name)
+
+
+@pytest.mark.parametrize("mode", ["0", "3", "5"])
+def test_head_stage_table_forward_forms(mode, monkeypatch):
+    monkeypatch.setenv("STGCN_HEAD_FUSE", mode)
+    _table_case("d")
+
+
+@pytest.mark.parametrize("name", ["h", "b"])
+def test_head_stage_table_fused_mse_loss(name):
+    _table_case(name, loss_scale=0.5)
+
+
+@pytest.mark.parametrize("name", ["a", "b", "g", "h", "j"])
+def test_head_stage_table_bf16(name):
+    from tests.test_gpu_head import head_bf16_case
+    head_bf16_case("cpu", name)
+
+
+@pytest.mark.parametrize("n_his", [11, 13])
+def test_model_with_a_non_dense_head(n_his):
+    from tests.test_gpu_head import model_case
+    model_case("cpu", n_his)
