@@ -1,124 +1,22 @@
-"""Helpers for the -m gpu tests: run one ST block through the HIP library on cuda:0 and compare every
-stage with the numpy stage oracle."""
-import numpy as np
-import torch
-
-from oracle import stblock_stages as st
-from stgcn_amd import _lib, ops
-from tests.emu_util import block_case, nonsym_gso, params_in_field_order
+"""Helpers for the -m gpu tests: run one ST block through the HIP library on cuda:0 and compare every stage with the numpy stage
+oracle.  The harness itself is tests/block_util.py, which the emulator tests share."""
+from tests import block_util
+from tests.block_util import FWD_TOL, GRAD_TOL      # noqa: F401  (tests/head_util.py and the bf16 helpers import the bars from here)
 
 
 def bind_hip():
-    L = _lib.use_library(_lib.DEFAULT_LIB)
-    assert L.backend == "hip-gfx950", "GPU tests must run on the HIP library, not the emulator"
-    return L
+    return block_util.bind("cuda:0")
 
 
-def run_block_case(c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso=None, dev="cuda:0", seed=99, offset=3, pdrop=0.5):
-    """Returns dict of max errors (absolute for activations, relative-to-max for gradients)."""
+def run_block_case(c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso=None, dev="cuda:0", seed=99, offset=3, pdrop=0.5,
+                   debug_stages=True):
+    """Returns dict of max errors (absolute for activations, relative-to-max for gradients): block_util.run_block_case on the HIP
+    library.  debug_stages=True: the fused kernels' on-chip intermediates (dZ2, dZ1) come from the stage-per-launch kernels, launched in
+    front of them; False: the launch sequence of a training step.  Either way the previous setting of the flag is restored on return."""
     bind_hip()
-    ops.set_debug_stages(True)      # fused kernels also write the intermediates they keep on chip (dZ2)
-    cfg, p = block_case(c_in, channels, Kt, Ks, gct, act, N, B, T)
-    if gso is None:
-        gso = nonsym_gso(N, 5)
-    rs = np.random.RandomState(11)
-    x_np = rs.standard_normal((B, c_in, T, N)).astype(np.float32)
-    T2 = T - 2 * (Kt - 1)
-    dy_np = rs.standard_normal((B, channels[2], T2, N)).astype(np.float32)
-    bcfg = ops.BlockConfig(Kt=Kt, Ks=Ks, n_vertex=N, c_in=c_in, channels=tuple(channels), act_func=act, graph_conv_type=gct,
-                           droprate=pdrop)
-    gp, gt = ops.gso_prepare(torch.from_numpy(gso).to(dev), ops.graph_terms(bcfg))
-    params = [None if t is None else t.clone().to(dev).requires_grad_(True) for t in params_in_field_order(p, "st_blocks.0.", gct)]
-    x = torch.from_numpy(x_np).to(dev).requires_grad_(c_in > 1)
-    wsc = ops.WorkspaceCache()
-    y = ops.st_conv_block(x, gp, gt, bcfg, params, training, seed, offset, wsc)
-    y.backward(torch.from_numpy(dy_np).to(dev))
-    torch.cuda.synchronize()
-
-    cl = lambda a: np.ascontiguousarray(a.transpose(0, 2, 3, 1)).astype(np.float64)
-    keep = None
-    if training:
-        ks = ops.dropout_mask(B * T2 * N * channels[2], pdrop, seed, offset, dev).cpu().numpy().reshape(B, T2, N, channels[2])
-        keep = (ks > 0).astype(np.float64)
-    g64 = gso.astype(np.float64)
-    bp = st.block_params_np(p, "st_blocks.0.", gct, np.float64)
-    y_ref, sv = st.stblock_fwd(cl(x_np), g64, bp, Kt, c_in, channels, gct, act, keep, pdrop)
-    dx_ref, g_ref = st.stblock_bwd(cl(dy_np), sv, g64, bp, Kt, c_in, channels, gct, act, pdrop, need_dx=c_in > 1)
-
-    desc = ops.make_desc(bcfg, B, T, training, c_in > 1)
-    plan = ops.query_plan(desc)
-    ws = wsc.buf.cpu().numpy()
-    # the autograd ctx keeps `saved`; fetch it again through a second forward into our own buffer
-    import ctypes as C
-    L = _lib.lib()
-    saved = torch.empty(plan.saved_floats, device=dev)
-    y2 = torch.empty_like(y.permute(0, 2, 3, 1).contiguous())
-    pst = ops._param_struct(_lib.StblockParams, [None if t is None else t.detach() for t in params])
-    x_cl = x.detach().permute(0, 2, 3, 1).contiguous()
-    ws2 = torch.empty(plan.ws_floats, device=dev)
-    L.check(L.dll.stgcn_stblock_forward(C.byref(desc), C.byref(pst), x_cl.data_ptr(), gp.data_ptr(), y2.data_ptr(), saved.data_ptr(),
-                                        ws2.data_ptr(), seed, offset, None, torch.cuda.current_stream().cuda_stream), "fwd")
-    torch.cuda.synchronize()
-    svn = saved.cpu().numpy()
-    T1 = plan.T1
-    c0, c1, c2 = channels
-    terms = 2 if gct == "graph_conv" else Ks
-
-    def seg(buf, off, ref):
-        return float(np.abs(buf[off:off + ref.size].reshape(ref.shape) - ref).max())
-
-    err = {}
-    # chained launches: the sticky error word (a bounded wait gave up) of both workspaces, and ticket / finished-workgroup words re-armed
-    for nm, buf in (("autograd", wsc.buf), ("direct", ws2)):
-        cw = buf[plan.ws_chain:plan.ws_chain + 4].view(torch.int32).cpu().numpy()
-        err[f"grad_none_ok.chain_words_{nm}"] = float(abs(cw[:3]).sum())
-    if not plan.recompute_tc1:
-        err["fwd.U1"] = seg(svn, plan.sv_U1, sv["U1"])
-        err["fwd.S1"] = seg(svn, plan.sv_S1, sv["S1"])
-    err["fwd.A"] = seg(svn, plan.sv_A, sv["A"])
-    for k in range(1, terms):
-        err[f"fwd.X{k}"] = seg(svn, plan.sv_Xk + (k - 1) * B * T1 * N * c1, sv["Xs"][k])
-    err["fwd.G"] = seg(svn, plan.sv_G, sv["G"])
-    err["fwd.U2"] = seg(svn, plan.sv_U2, sv["U2"])
-    err["fwd.S2"] = seg(svn, plan.sv_S2, sv["S2"])
-    err["fwd.mean"] = seg(svn, plan.sv_mean, sv["mean"])
-    err["fwd.rstd_rel"] = float(np.abs(svn[plan.sv_rstd:plan.sv_rstd + B * T2].reshape(B, T2) / sv["rstd"] - 1).max())
-    err["fwd.y"] = float(np.abs(cl(y.detach().cpu().numpy()) - y_ref).max())
-    err["fwd.y_repeat_bitwise"] = float((y2 != y.detach().permute(0, 2, 3, 1)).sum().item())
-
-    rel = lambda got, ref: float(np.abs(got - ref).max() / max(1e-30, np.abs(ref).max()))
-    dH2, _, _ = st.ln_dropout_bwd(cl(dy_np), sv["H2"], bp["ln_w"], sv["mean"], sv["rstd"], keep, pdrop)
-    dZ2 = st.gate_bwd(dH2, sv["U2"], sv["S2"], act)
-    err["bwd.dZ2"] = rel(ws[plan.ws_dZ2:plan.ws_dZ2 + dZ2.size].reshape(dZ2.shape), dZ2)
-    dG = st.tconv_bwd_data(dZ2, sv["W2"], Kt, c1)
-    dYg = dG * (sv["G"] > 0)
-    err["bwd.dYg"] = rel(ws[plan.ws_dYg:plan.ws_dYg + dYg.size].reshape(dYg.shape), dYg)
-    dA, _, _ = st.gconv_bwd(dG, sv["G"], sv["Xs"], g64, sv["Wk"])
-    err["bwd.dA"] = rel(ws[plan.ws_dA:plan.ws_dA + dA.size].reshape(dA.shape), dA)
-    dZ1 = st.gate_bwd(dA @ sv["Wa"].T, sv["U1"], sv["S1"], act)
-    if not (plan.thin_tc1 and c_in == 1):      # the thin first layer keeps dZ1 on chip unless dx is needed
-        err["bwd.dZ1"] = rel(ws[plan.ws_dZ1:plan.ws_dZ1 + dZ1.size].reshape(dZ1.shape), dZ1)
-    if c_in > 1:
-        err["bwd.dx"] = rel(cl(x.grad.cpu().numpy()), dx_ref)
-    for name, prm in zip(_lib.PARAM_FIELDS, params):
-        ref = g_ref[name]
-        if prm is None:
-            continue
-        if ref is None:
-            err["grad_none_ok." + name] = 0.0 if prm.grad is None else 1.0
-            continue
-        err["grad." + name] = rel(prm.grad.cpu().numpy().astype(np.float64), ref.reshape(prm.shape)) if prm.grad is not None else float("inf")
-    return err
-
-
-FWD_TOL = 1e-4     # north star: activations within 1e-4 abs of the reference CPU path
-GRAD_TOL = 1e-3    # north star / SURVEY.md 8d: gradients rtol 1e-3
+    return block_util.run_block_case(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso=gso, seed=seed, offset=offset,
+                                     pdrop=pdrop, debug_stages=debug_stages, oracle32=False, kink=False)
 
 
 def assert_errors(err):
-    bad = {}
-    for k, v in err.items():
-        tol = 0.0 if (k.startswith("grad_none_ok") or k.endswith("bitwise")) else (FWD_TOL if k.startswith("fwd.") else GRAD_TOL)
-        if not (v <= tol):
-            bad[k] = v
-    assert not bad, f"out of tolerance: {bad}\nall: {err}"
+    block_util.assert_errors(err)
