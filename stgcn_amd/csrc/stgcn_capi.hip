@@ -14,6 +14,7 @@
 #include "stgcn_kernels_gctile.hip.h"
 #include "stgcn_kernels_gcslab16.hip.h"
 #include "stgcn_kernels_head.hip.h"
+#include "stgcn_route.h"
 
 using namespace stgcn;
 
@@ -26,16 +27,6 @@ int g_gemm_big_nt = 0;   // stgcn_set_gemm_big_nt: forced column extent of the b
 
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
-// Where the backward takes the dropout mask of a block's LayerNorm from (tc2_bwd_kernel, the stgcn_ln_hook epilogues): read off the block
-// output y -- the forward stores a dropped element as -0.0 and a kept exact zero as +0.0 (drop_encode, stgcn_device.hip.h), so the test is
-// exact (round 4's "kept iff y != 0" lost a kept zero: ADVICE r4) -- or regenerated (Philox: ~100 VALU instructions per 4 elements in the
-// consumers' time steps; measured on C2 fp32, pass r5-01: tc2_bwd 29.1 + 21.1 -> 28.3 + 20.2 us, tc1_bwd 61.7 -> 60.1, step 0.3756 -> 0.3679 ms).
-// STGCN_HOOK_MASK=philox / y forces one (tests run both forms of both types).
-inline bool hook_mask_from_y() {   // (the default is the same for fp32 and bf16 activations since round 5)
-    const char* e = getenv("STGCN_HOOK_MASK");
-    if (e && e[0] == 'p') return false;
-    return true;
-}
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -43,9 +34,12 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-
-inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+template <typename T>
+T zeroed() {   // kernel argument blocks start all-zero
+    T t;
+    memset(&t, 0, sizeof(t));
+    return t;
+}
 
 // ---- optional per-kernel timing: hipEvent pairs around every launch (off by default) ---------------
 struct ProfSlot { const char* name; int tag; hipEvent_t e0, e1; };
@@ -82,8 +76,7 @@ inline void launch_log(const char* label, const char* kernel, dim3 grid, dim3 bl
 #ifdef STGCN_EMU_RACE
     emu::g.kname = kernel;   // (LDS race-check build of the CPU emulator: names the launch in its reports)
 #endif
-    static FILE* f = getenv("STGCN_LAUNCH_LOG") ? fopen(getenv("STGCN_LAUNCH_LOG"), "w") : nullptr;
-    if (f) {
+    if (FILE* f = launch_log_file()) {
         fprintf(f, "%s@%d\t%s\t%u\t%u\n", label, g_prof_tag, kernel, grid.x * grid.y * grid.z, block.x * block.y * block.z);
         fflush(f);
     }
@@ -100,30 +93,24 @@ inline void launch_log(const char* label, const char* kernel, dim3 grid, dim3 bl
         if (e_ != hipSuccess) return fail(STGCN_ERR_LAUNCH, "%s: %s", label, hipGetErrorString(e_)); \
     } while (0)
 
-// launch a kernel whose template arguments mention ET, instantiated for the activation type of the call (g_bf16)
-#define STGCN_LAUNCH_ET(label, st, kernel, grid, block, lds, ...)                                 \
+// the same launch with ET = T_ in scope, for kernels whose template arguments mention ET
+#define STGCN_LAUNCH_AS(T_, ...)                                                                  \
     do {                                                                                          \
-        if (g_bf16) {                                                                             \
-            using ET = bf16;                                                                      \
-            STGCN_LAUNCH(label, st, kernel, grid, block, lds, __VA_ARGS__);                       \
-        } else {                                                                                  \
-            using ET = float;                                                                     \
-            STGCN_LAUNCH(label, st, kernel, grid, block, lds, __VA_ARGS__);                       \
-        }                                                                                         \
+        using ET = T_;                                                                            \
+        STGCN_LAUNCH(__VA_ARGS__);                                                                \
     } while (0)
-// the same for BACKWARD kernels: fp32 blocks take ET = f32x (bf16x3 products) when stgcn_set_bwd_precision(1) is in force
-#define STGCN_LAUNCH_ETB(label, st, kernel, grid, block, lds, ...)                                \
+// ... instantiated for the activation type of the call (g_bf16)
+#define STGCN_LAUNCH_ET(...)                                                                      \
     do {                                                                                          \
-        if (g_bf16) {                                                                             \
-            using ET = bf16;                                                                      \
-            STGCN_LAUNCH(label, st, kernel, grid, block, lds, __VA_ARGS__);                       \
-        } else if (g_bwd_precision == 1) {                                                        \
-            using ET = f32x;                                                                      \
-            STGCN_LAUNCH(label, st, kernel, grid, block, lds, __VA_ARGS__);                       \
-        } else {                                                                                  \
-            using ET = float;                                                                     \
-            STGCN_LAUNCH(label, st, kernel, grid, block, lds, __VA_ARGS__);                       \
-        }                                                                                         \
+        if (g_bf16) STGCN_LAUNCH_AS(bf16, __VA_ARGS__);                                           \
+        else STGCN_LAUNCH_AS(float, __VA_ARGS__);                                                 \
+    } while (0)
+// ... for BACKWARD kernels: fp32 blocks take ET = f32x (bf16x3 products) when stgcn_set_bwd_precision(1) is in force
+#define STGCN_LAUNCH_ETB(...)                                                                     \
+    do {                                                                                          \
+        if (g_bf16) STGCN_LAUNCH_AS(bf16, __VA_ARGS__);                                           \
+        else if (g_bwd_precision == 1) STGCN_LAUNCH_AS(f32x, __VA_ARGS__);                        \
+        else STGCN_LAUNCH_AS(float, __VA_ARGS__);                                                 \
     } while (0)
 #define STGCN_ETB_VALUE(expr) (g_bf16 ? [&] { using ET = bf16; return (expr); }() : g_bwd_precision == 1 ? [&] { using ET = f32x; return (expr); }() : [&] { using ET = float; return (expr); }())
 // value of an expression that mentions ET (e.g. wg_capacity of a kernel instantiation)
@@ -132,12 +119,6 @@ inline void launch_log(const char* label, const char* kernel, dim3 grid, dim3 bl
 #define STGCN_F32_ONLY(what)                                                                      \
     do {                                                                                          \
         if (g_bf16) return fail(STGCN_ERR_UNSUPPORTED, "%s: no bf16 variant (bf16 blocks need the fused time-stepping kernels)", what); \
-    } while (0)
-
-#define STGCN_CHECK_LAUNCH(name)                                                                  \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) return fail(STGCN_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
 int check_desc(const stgcn_stblock_desc* d) {
@@ -172,40 +153,6 @@ int check_desc(const stgcn_stblock_desc* d) {
     return STGCN_OK;
 }
 
-// workgroups (4 waves) of the forward: two 16-row tiles per wave, at most four workgroups per CU
-inline int thin_fwd_wgs(int64_t rows) {
-    constexpr int tpw = 2;   // tiles per wave
-    const int64_t tiles = (rows + 15) / 16, want = (tiles + 4 * tpw - 1) / (4 * tpw), cap = 4L * device_cus();
-    return (int)(want < 1 ? 1 : want < cap ? want : cap);
-}
-
-inline int terms(const stgcn_stblock_desc* d) { return d->graph_conv == STGCN_GC_KIPF ? 2 : d->Ks; }
-
-struct Derived {
-    int T1, T2, NP, KP1, KP2, NC1, NC2, CP_in, CP1, terms, tiled;
-    int64_t rows0, rows1, rows2, slabs1, slabs2;
-};
-Derived derive(const stgcn_stblock_desc* d) {
-    Derived v;
-    v.T1 = d->T - d->Kt + 1;
-    v.T2 = v.T1 - d->Kt + 1;
-    v.terms = terms(d);
-    v.tiled = gc_is_tiled(d->N, v.terms) ? 1 : 0;
-    v.NP = gc_padded_nodes(d->N, v.terms);
-    v.KP1 = (int)rup((int64_t)d->Kt * d->c_in, 16);
-    v.KP2 = (int)rup((int64_t)d->Kt * d->c1, 16);
-    v.NC1 = 2 * d->c0;
-    v.NC2 = 2 * d->c2;
-    v.CP_in = (int)rup(d->c_in, 16);
-    v.CP1 = (int)rup(d->c1, 16);
-    v.rows0 = (int64_t)d->B * d->T * d->N;
-    v.rows1 = (int64_t)d->B * v.T1 * d->N;
-    v.rows2 = (int64_t)d->B * v.T2 * d->N;
-    v.slabs1 = (int64_t)d->B * v.T1;
-    v.slabs2 = (int64_t)d->B * v.T2;
-    return v;
-}
-
 uint32_t drop_thresh(float p) {
     double t = (double)p * 4294967296.0;
     if (t > 4294967295.0) t = 4294967295.0;
@@ -224,12 +171,6 @@ int wg_capacity(K kernel, int threads, size_t lds) {
     const void* key = reinterpret_cast<const void*>(kernel);
     for (int i = 0; i < n; ++i)
         if (cache[i].k == key && cache[i].threads == threads && cache[i].lds == lds) return cache[i].cap;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
     int nb = 0;
     // a block the kernel cannot be launched with at all (more threads than its __launch_bounds__, more LDS than a CU has) gets capacity 0:
     // the launch heuristics then never pick that geometry (a failed query used to read as "one workgroup per CU")
@@ -237,7 +178,7 @@ int wg_capacity(K kernel, int threads, size_t lds) {
         (void)hipGetLastError();
         nb = 0;
     }
-    const int cap = nb * cus;
+    const int cap = nb * runtime_cus();
     if (n < 64) cache[n++] = Entry{key, threads, lds, cap};
     return cap;
 }
@@ -259,9 +200,8 @@ struct PackList {
         return true;
     }
 };
-bool pack_fill_block(PackList& L, const stgcn_stblock_desc* d, const stgcn_stblock_params* P, const stgcn_stblock_plan& pl, float* ws,
-                     bool all) {
-    const Derived v = derive(d);
+bool pack_fill_block(PackList& L, const stgcn_stblock_desc* d, const BlockRoute& v, const stgcn_stblock_params* P, const stgcn_stblock_plan& pl,
+                     float* ws, bool all) {
     bool ok = true;
     ok &= L.add(PK_TCONV_FWD, v.NC1 * v.KP1, ws + pl.ws_W1p, P->tc1_w, P->tc1_b, P->tc1_aw, P->tc1_ab, d->c_in, d->c0, d->Kt, v.KP1 / 16);
     if (d->need_dx || all)
@@ -275,12 +215,11 @@ bool pack_fill_block(PackList& L, const stgcn_stblock_desc* d, const stgcn_stblo
     ok &= L.add(PK_TCONV_BWD, d->Kt * v.NC2 * v.CP1, ws + pl.ws_W2d, P->tc2_w, P->tc2_b, P->tc2_aw, P->tc2_ab, d->c1, d->c2, d->Kt,
                 d->Kt * v.NC2 / 16);
     ok &= L.add(PK_TCONV_BIAS, v.NC2, ws + pl.ws_b2, P->tc2_w, P->tc2_b, P->tc2_aw, P->tc2_ab, d->c1, d->c2, d->Kt, 0);
-    const bool k3s = (tc1_bwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt) || tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt)) && (d->Kt * d->c_in > 4);
-    if (pl.recompute_tc1 || k3s)
+    if (v.dense_W1)
         ok &= L.add(PK_TCONV_DENSE, v.KP1 * v.NC1, ws + pl.ws_W1dense, P->tc1_w, P->tc1_b, P->tc1_aw, P->tc1_ab, d->c_in, d->c0, d->Kt, 0);
-    if (k3s && !pl.thin_tc1)
+    if (v.dense_Wa)
         ok &= L.add(PK_ALIGN_DENSE, d->c0 * d->c1, ws + pl.ws_WaDense, P->al_w, P->al_b, nullptr, nullptr, d->c0, d->c1, 1, 0);
-    if (pl.fused_tc2_bwd)
+    if (v.dense_W2)
         ok &= L.add(PK_TCONV_DENSE, v.KP2 * v.NC2, ws + pl.ws_W2dense, P->tc2_w, P->tc2_b, P->tc2_aw, P->tc2_ab, d->c1, d->c2, d->Kt, 0);
     ok &= L.add(PK_ZERO, (int)pl.chain_words, ws + pl.ws_chain, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0);   // control words of the chained launches
     return ok;
@@ -290,12 +229,6 @@ int launch_pack_list(const char* label, PackList& L, hipStream_t st) {
     L.pa.njobs = L.nj;
     STGCN_LAUNCH(label, st, pack_kernel, dim3(L.pa.start[L.nj]), dim3(kThreads), 0, L.pa);
     return STGCN_OK;
-}
-int launch_pack(const stgcn_stblock_desc* d, const stgcn_stblock_params* P, const stgcn_stblock_plan& pl, float* ws,
-                       hipStream_t st) {
-    PackList L;
-    if (!pack_fill_block(L, d, P, pl, ws, false)) return fail(STGCN_ERR_INVALID, "pack job table overflow");
-    return launch_pack_list("pack", L, st);
 }
 
 // ---- the model's weight pack rides on the first launch that follows it (round 6) ------------------------------------------------------
@@ -309,14 +242,6 @@ struct PendingPack {
     hipStream_t st = nullptr;
 };
 thread_local PendingPack g_pending_pack;
-// "bf16x6" product form of the fp32 blocks (Frag3, stgcn_device.hip.h): fp32-accurate products on the bf16 matrix pipe, operands split once at
-// their producer -- the default of tc1_fwd / tc2_ln_fwd / tc1_bwd since round 6 (measured error against the fp64 stage oracle equal to the
-// fp32-MFMA path's, profiles/r6-29_x6_errors.txt).  STGCN_MFMA_X6=0 selects v_mfma_f32_16x16x4_f32 for every product (read per call: bench.py
-// reports that step as config.secondary_fp32_mfma, the stage tests run both).
-inline bool mfma_x6() {
-    const char* e = getenv("STGCN_MFMA_X6");
-    return !(e && e[0] == '0');
-}
 int flush_pending_pack() {
     if (!g_pending_pack.valid) return STGCN_OK;
     g_pending_pack.valid = false;
@@ -337,8 +262,7 @@ int launch_ln_fwd(const char* label, LnFwdArgs ln, int64_t slabs, hipStream_t st
     ln.per = 1024;                                   // float4 columns per workgroup (4 per thread)
     const dim3 grid(cdiv(n4, ln.per), (unsigned)slabs), blk(kThreads);
     ln.stats_ready = 0;
-    static const int min_chunks = getenv("STGCN_LN_STATS_MIN_CHUNKS") ? atoi(getenv("STGCN_LN_STATS_MIN_CHUNKS")) : 8;   // (test knob)
-    if ((int)grid.x >= min_chunks) {   // many chunks per slab: the statistics once per slab instead of once per chunk
+    if ((int)grid.x >= ln_stats_min_chunks()) {   // many chunks per slab: the statistics once per slab instead of once per chunk
         STGCN_LAUNCH("ln_slab_stats", st, ln_slab_stats_kernel, dim3((unsigned)slabs), blk, 64, ln);
         ln.stats_ready = 1;
     }
@@ -350,7 +274,7 @@ template <int NT>
 int launch_tconv_fwd_nt(const char* label, const TconvFwdArgs& a, hipStream_t st) {
     // candidates: 16 / 32 / 48-row tiles with 4 waves, 64-row tiles with 8 waves.  Smallest tile (most workgroups) whose
     // grid is resident in one round; otherwise the fewest rounds.  STGCN_TCONV_TR=<rows> forces a tile (tuning knob).
-    static const int force_tr = getenv("STGCN_TCONV_TR") ? atoi(getenv("STGCN_TCONV_TR")) : 0;
+    const int force_tr = force_tconv_tile_rows();
     const int trs[4] = {16, 32, 48, 64};
     int best = -1, best_rounds = 1 << 30;
     for (int i = 0; i < 4; ++i) {
@@ -383,8 +307,7 @@ int launch_tconv_fwd_nt(const char* label, const TconvFwdArgs& a, hipStream_t st
 }
 // v4: 32-row x 256-column tiles with streamed, double-buffered weight rounds (the output head; see tconv_fwd4_kernel)
 inline bool tconv4_ok(const TconvFwdArgs& a) {
-    static const int off = getenv("STGCN_TCONV4") ? atoi(getenv("STGCN_TCONV4")) == 0 : 0;   // A/B knob
-    return !off && a.Cout == 128 && (a.ts.C & 3) == 0 && a.KCH * 16 == a.ts.taps * a.ts.C && !a.Wap && !a.H &&
+    return !tconv4_off() && a.Cout == 128 && (a.ts.C & 3) == 0 && a.KCH * 16 == a.ts.taps * a.ts.C && !a.Wap && !a.H &&
            (size_t)tconv2_lds_floats(a.KCH * 16, 256, 32) * sizeof(float) <= 64 * 1024;
 }
 // Rows of a head tile.  The C2 head has B * N = 6624 rows: 207 tiles of 32 rows leave 49 CUs idle and give every other CU ONE workgroup.
@@ -392,10 +315,7 @@ inline bool tconv4_ok(const TconvFwdArgs& a) {
 // 18.6 to 20.4 us (its 256 KB weight stream per workgroup does not shrink with the tile) -- so the fc kernels default to 16 rows, the
 // conv / transposed conv to 32 (their 16-row instances stay compiled).  STGCN_HEAD_FC_TILE = 16 | 32 overrides the fc tile.
 inline int head_tile_rows() { return 32; }
-inline int head_fc_tile_rows() {
-    const char* e = getenv("STGCN_HEAD_FC_TILE");   // (read per call: the tests switch it)
-    return (e && atoi(e) == 32) ? 32 : 16;
-}
+inline int head_fc_tile_rows() { return head_fc_tile_knob() == 32 ? 32 : 16; }
 template <bool PLAIN>
 int launch_tconv_fwd4(const char* label, const Tconv4Args& aa, hipStream_t st) {
     constexpr int KC = 4;
@@ -412,8 +332,7 @@ int launch_tconv_fwd4(const char* label, const Tconv4Args& aa, hipStream_t st) {
 }
 int launch_tconv_fwd(const char* label, const TconvFwdArgs& a, hipStream_t st) {
     if (tconv4_ok(a)) {
-        Tconv4Args aa;
-        memset(&aa, 0, sizeof(aa));
+        Tconv4Args aa = zeroed<Tconv4Args>();
         aa.f = a;
         return launch_tconv_fwd4<false>(label, aa, st);
     }
@@ -435,16 +354,6 @@ inline GcGeom gc_geom(int HT, int want_parts) {
     g.maxq = (per + g.waves - 1) / g.waves;
     return g;
 }
-inline void gc_parts_override(int& fwd, int& bwd) {
-    static int f = 0, b = 0, init = 0;
-    if (!init) {
-        init = 1;
-        const char* e = getenv("STGCN_GC_PARTS");
-        if (e) sscanf(e, "%d,%d", &f, &b);
-    }
-    if (f > 0) fwd = f;
-    if (b > 0) bwd = b;
-}
 
 // ---- tiled graph conv (stgcn_kernels_gctile.hip.h): one GEMM launch per operator term + one row pass -----------------
 template <int NTW>
@@ -456,14 +365,13 @@ int launch_gso_gemm_ntw(const char* label, GsoGemmArgs g, hipStream_t st) {
 int launch_gso_gemm(const char* label, const float* M, const float* X, float alpha, const float* Z1, float b1, const float* Z2, float b2,
                     float* out, int N, int NP, long slabs, hipStream_t st) {
     STGCN_F32_ONLY(label);
-    GsoGemmArgs g;
-    memset(&g, 0, sizeof(g));
+    GsoGemmArgs g = zeroed<GsoGemmArgs>();
     g.M = M; g.X = X; g.Z1 = Z1; g.Z2 = Z2; g.out = out; g.alpha = alpha; g.b1 = b1; g.b2 = b2;
     g.N = N; g.NP = NP; g.slabs = slabs;
     g.row_tiles = cdiv(N, kGtBM);
     // column extent of the workgroup tile (2 * NTW slabs): the launch costs rounds-of-resident-workgroups x work per
     // workgroup (~NTW); ties go to the wider tile (fewer operator re-reads).  STGCN_GEMM_NTW=<3|4|5> forces one (tuning knob).
-    static const int force = getenv("STGCN_GEMM_NTW") ? atoi(getenv("STGCN_GEMM_NTW")) : 0;
+    const int force = force_gemm_ntw();
     int best = 4;
     long best_cost = -1;
     for (int ntw = 5; ntw >= 3; --ntw) {
@@ -495,8 +403,7 @@ int launch_pack_operand(const float* X, int N, int NP, long slabs, OperandBuf o,
 }
 int launch_gso_gemm_bf16(const char* label, const float* Mpad, OperandBuf x, float alpha, const float* Z1, float b1, const float* Z2, float b2,
                          float* out, const OperandBuf* next, int N, int NP, long slabs, hipStream_t st) {
-    GsoGemmBfArgs g;
-    memset(&g, 0, sizeof(g));
+    GsoGemmBfArgs g = zeroed<GsoGemmBfArgs>();
     const size_t M = (size_t)NP * NP;
     g.LD = gc_plane_ld(NP);
     g.Mh = Mpad + M; g.Ml = Mpad + M + (size_t)NP * g.LD / 2;
@@ -508,12 +415,12 @@ int launch_gso_gemm_bf16(const char* label, const float* Mpad, OperandBuf x, flo
     g.col_tiles = (int)(gc_operand_cols(slabs) / 128);
     const dim3 grid((unsigned)(g.row_tiles * g.col_tiles));
     // depth of a pipeline step: 32 (more workgroups per CU) or 64 bf16 (half as many barriers); STGCN_GEMM_BF16_BK forces one
-    static const int force_bk = getenv("STGCN_GEMM_BF16_BK") ? atoi(getenv("STGCN_GEMM_BF16_BK")) : 0;
+    const int force_bk = force_gemm_bf16_bk();
     const int bk = force_bk == 32 || force_bk == 64 ? force_bk : kGbDefaultBK;
     const int split = g_gc_precision == 1 && !g_bf16;   // (bf16 activations: operands are bf16 numbers already, one MFMA per product)
     {   // 256 x (32 * NT) tiles, one workgroup per CU (gso_gemm_bf16_big_kernel); the 128 x 128 kernel otherwise
         const int force_nt = g_gemm_big_nt;   // stgcn_set_gemm_big_nt (tests force every instance)
-        static const int big_bk = getenv("STGCN_GEMM_BIG_BK") && atoi(getenv("STGCN_GEMM_BIG_BK")) == 32 ? 32 : 64;   // r3-17: 64-deep steps 6 % faster
+        const int big_bk = gemm_big_bk();
         if (!split && NP % kGbBigBM == 0) {
             const long CP = gc_operand_cols(slabs);
             const int rts = NP / kGbBigBM, cus = device_cus();
@@ -586,8 +493,7 @@ int launch_gconv_fwd_tiled(const GconvFwdArgs& a, hipStream_t st) {
         }
         if (rc) return rc;
     }
-    GcRowsFwdArgs r;
-    memset(&r, 0, sizeof(r));
+    GcRowsFwdArgs r = zeroed<GcRowsFwdArgs>();
     r.X0 = a.A; r.Xk = a.Xk; r.W = a.W; r.bias = a.bias; r.G = a.G; r.rows = a.slabs * a.N; r.kstride = ks; r.terms = a.Ks; r.kipf = a.kipf;
     const long tiles = (r.rows + 15) / 16;
     const long wgs = (tiles + 3) / 4;
@@ -602,8 +508,7 @@ int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st) {
     const long ks = a.slabs * a.N * 16;                 // elements per term
     const long ksf = g_bf16 ? ks / 2 : ks;              // ... in the 4-byte units of the float* slots
     const int K = a.Ks - 1;
-    GcRowsBwdArgs r;
-    memset(&r, 0, sizeof(r));
+    GcRowsBwdArgs r = zeroed<GcRowsBwdArgs>();
     r.dY = a.dY; r.X0 = a.X0; r.Xk = a.Xk; r.W = a.W; r.part = a.part; r.rows = a.slabs * a.N; r.kstride = ks; r.gstride = ks;
     r.Gk = K == 0 ? a.dA : a.Gk;   // a single term: g_0 (+ dY) is dA itself
     r.terms = a.Ks; r.kipf = a.kipf; r.tiles_per_wg = a.tiles_per_wg;
@@ -634,8 +539,8 @@ int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st) {
     return launch_gso_gemm("gso_gemm_bwd", a.LTp, gk(1), 1.f, gk(0), 1.f, K >= 2 ? gk(2) : nullptr, -1.f, a.dA, a.N, a.NP, a.slabs, st);
 }
 
-int launch_gconv_fwd(GconvFwdArgs a, hipStream_t st) {
-    if (gc_is_tiled(a.N, a.Ks)) return launch_gconv_fwd_tiled(a, st);
+int launch_gconv_fwd(GconvFwdArgs a, bool tiled, hipStream_t st) {
+    if (tiled) return launch_gconv_fwd_tiled(a, st);
     const int HT = a.NP / 16;
     int pf = (HT + 3) / 4, pb = 1;
     gc_parts_override(pf, pb);
@@ -676,7 +581,7 @@ int launch_bwd_data(const char* label, const TconvBwdDataArgs& a, int ntt, hipSt
     else if (ntt == 4) {
         // 8 waves x 2 m-tiles (more waves in flight) unless its register budget leaves part of the grid to a second round
         // and the 4-wave x 4 m-tile variant does not
-        static const int force_w = getenv("STGCN_BWD_DATA_WAVES") ? atoi(getenv("STGCN_BWD_DATA_WAVES")) : 0;   // tuning knob
+        const int force_w = force_bwd_data_waves();   // tuning knob
         const int r8 = force_w ? (force_w == 8 ? 0 : 2) : rounds_of(tiles, wg_capacity(tconv_bwd_data_kernel<2, 1, 0, 8>, 512, lds));
         const int r4 = force_w ? 1 : rounds_of(tiles, wg_capacity(tconv_bwd_data_kernel<4, 1, 0, 4>, 256, lds));
         if (r8 <= r4) STGCN_LAUNCH(label, st, (tconv_bwd_data_kernel<2, 1, 0, 8>), grid, dim3(512), lds, a);
@@ -686,16 +591,6 @@ int launch_bwd_data(const char* label, const TconvBwdDataArgs& a, int ntt, hipSt
     return STGCN_OK;
 }
 
-// The head's forward as ONE launch (head_fwd_kernel, stgcn_kernels_fwd.hip.h): default on; STGCN_HEAD_FUSE=0 restores the conv + fc launches
-// (A/B runs), 2 / 4 admit only the 32- / 64-row tile (tests).  The exchange of the row statistics relies on write-through stores.
-inline int head_fuse_mode() {
-#if !STGCN_WT_STORES
-    return 0;
-#else
-    const char* e = getenv("STGCN_HEAD_FUSE");
-    return e ? atoi(e) : 1;
-#endif
-}
 // job waves of gconv_bwd2_kernel: one per parameter-gradient job of the part (Ks weight terms + the bias, spread over the parts), but never
 // more than the kernel's __launch_bounds__(768) leaves beside the tile waves -- the job loop strides by the job-wave count, so fewer waves
 // only walk more jobs each (Ks >= 4 with one part asked for 13+ waves and the launch failed)
@@ -703,13 +598,13 @@ inline int gcbwd2_job_waves(int Ks, int parts, int nwa) {
     const int want = (Ks + 1 + parts - 1) / parts, room = 768 / 64 - nwa;
     return want < room ? want : room;
 }
-int launch_gconv_bwd(GconvBwdArgs a, hipStream_t st) {
-    if (gc_is_tiled(a.N, a.Ks)) return launch_gconv_bwd_tiled(a, st);
+int launch_gconv_bwd(GconvBwdArgs a, bool tiled, hipStream_t st) {
+    if (tiled) return launch_gconv_bwd_tiled(a, st);
     const int HT = a.NP / 16;
     int pf = 0, pb = 1;
     gc_parts_override(pf, pb);
     {   // round 3: slab split over parts, parameter-gradient jobs on their own waves (gconv_bwd2_kernel)
-        const int force_parts = getenv("STGCN_GCBWD2_PARTS") ? atoi(getenv("STGCN_GCBWD2_PARTS")) : 0;   // (read per call: the tests force geometries)
+        const int force_parts = force_gcbwd2_parts();
         // One node tile per tile wave (<= 8 tile waves per workgroup), and the whole grid resident in ONE round: every part re-stages the
         // slab's dY and re-forms all G_k, so a grid of SEVERAL parts that needs more rounds than the slab kernel costs more than it returns
         // (measured at the C3 size, 640 slabs x 3 parts on 512 slots: 120 us against 76 us; at C2, 320 x 2 on 768 slots: 27.2 against 30.0 us).
@@ -818,8 +713,7 @@ int launch_reduce_list(const char* label, ReduceList& L, hipStream_t st) {
     if (L.overflow) return fail(STGCN_ERR_INVALID, "%s: more than %d reduction jobs in one launch", label, kMaxReduceJobs);
     if (L.nj == 0) return STGCN_OK;
     L.ra.njobs = L.nj;
-    static const bool log_jobs = getenv("STGCN_REDUCE_LOG") != nullptr;   // diagnostic: the partial-sum tables one launch folds
-    if (log_jobs)
+    if (reduce_log())
         for (int i = 0; i < L.nj; ++i) {
             const ReduceJob& j = L.ra.job[i];
             fprintf(stderr, "[stgcn reduce] %s job %d: %ld elements x %d partials (%.2f MB read), %d workgroups\n", label, i,
@@ -833,8 +727,7 @@ int launch_reduce_list_optim(const char* label, ReduceList& L, int kind, const O
     if (L.overflow) return fail(STGCN_ERR_INVALID, "%s: more than %d reduction jobs in one launch", label, kMaxReduceJobs);
     if (L.nj == 0) return STGCN_OK;
     L.ra.njobs = L.nj;
-    ReduceOptimArgs a;
-    memset(&a, 0, sizeof(a));
+    ReduceOptimArgs a = zeroed<ReduceOptimArgs>();
     static_cast<ReduceArgs&>(a) = L.ra;
     a.x = x;
     if (kind == kOptNadamw)
@@ -843,8 +736,8 @@ int launch_reduce_list_optim(const char* label, ReduceList& L, int kind, const O
         STGCN_LAUNCH(label, st, reduce_kernel<kOptLion>, dim3(L.ra.start[L.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), a);
     return STGCN_OK;
 }
-void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const Derived& v, const BwdGeom& bg, const float* part,
-                       const stgcn_stblock_grads* G) {
+void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const BlockRoute& v, const float* part, const stgcn_stblock_grads* G) {
+    const BwdGeom& bg = v.bg;
     // dW_eff partials wp[P][..][NC] (ps floats apart), db_eff partials bp[P][NC] (pb floats apart)
     // The weight-gradient partials are stored TRANSPOSED, dW_eff^T[o][k*Cin + i] with LD floats per column o: the 4 rows a lane of the producing
     // MFMA tile holds for its column are then 16 contiguous bytes (one write-through store instead of four scattered dwords)
@@ -880,14 +773,11 @@ void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const Derived
     } else {
         add_tconv(bg.w2, d->c1, d->c2, G->tc2_w, G->tc2_b, G->tc2_aw, G->tc2_ab);
     }
-    if (bg.k3 && d->c0 > d->c1) {
-        const float* ap = part + bg.off_k3 + (long)d->Kt * d->c_in * v.NC1 + v.NC1;
-        L.add(G->al_w, ap, bg.k3_wgs, bg.k3_stride, 1, d->c0, d->c1, 0, d->c1, 1, 0, 1, d->c0);
-        L.add_flat(G->al_b, ap + (long)d->c0 * d->c1, bg.k3_wgs, bg.k3_stride, d->c1);
-    } else if (d->c0 > d->c1) {
-        // enumerate (i, j): src dWa[i][j] -> dst al_w[j][i]
-        L.add(G->al_w, part + bg.off_al, bg.al_wgs, bg.al_stride, 1, d->c0, d->c1, 0, d->c1, 1, 0, 1, d->c0);
-        L.add_flat(G->al_b, part + bg.off_al + (long)d->c0 * d->c1, bg.al_wgs, bg.al_stride, d->c1);
+    if (d->c0 > d->c1) {   // dWa | dba: behind dW_eff1 | db_eff1 in tc1_bwd_kernel's partials, else the align partials
+        const float* ap = bg.k3 ? part + bg.off_k3 + (long)d->Kt * d->c_in * v.NC1 + v.NC1 : part + bg.off_al;
+        const int Pn = bg.k3 ? bg.k3_wgs : bg.al_wgs, ps = bg.k3 ? bg.k3_stride : bg.al_stride;
+        L.add(G->al_w, ap, Pn, ps, 1, d->c0, d->c1, 0, d->c1, 1, 0, 1, d->c0);   // enumerate (i, j): src dWa[i][j] -> dst al_w[j][i]
+        L.add_flat(G->al_b, ap + (long)d->c0 * d->c1, Pn, ps, d->c1);
     }
     if (d->graph_conv == STGCN_GC_KIPF) L.add_flat(G->gc_w, part + bg.off_gc + 256, bg.gc_count, bg.gc_stride, 256);
     else L.add_flat(G->gc_w, part + bg.off_gc, bg.gc_count, bg.gc_stride, v.terms * 256);
@@ -896,9 +786,16 @@ void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const Derived
     L.add_flat(G->ln_w, part + bg.off_ln_g, bg.ln_sg, n, n);
     L.add_flat(G->ln_b, part + bg.off_ln_b, bg.ln_sg, n, n);
 }
+// a backward's dx_hook must describe the LayerNorm over this call's input gradient ([N, C] per slab, same dtype)
+int check_dx_hook(const char* who, const stgcn_ln_hook* h, int N, int C, int need_dx, int dtype) {
+    if (!h || !h->rowstat) return STGCN_OK;
+    if (h->N != N || h->C != C || !need_dx)
+        return fail(STGCN_ERR_INVALID, "%s: dx_hook describes a LayerNorm over [%d, %d], the input gradient is [%d, %d] per slab", who, h->N, h->C, N, C);
+    if (h->dtype != dtype) return fail(STGCN_ERR_INVALID, "%s: dx_hook describes tensors of another dtype than this call", who);
+    return STGCN_OK;
+}
 LnRowstatOut rowstat_out(const stgcn_ln_hook* h) {
-    LnRowstatOut o;
-    memset(&o, 0, sizeof(o));
+    LnRowstatOut o = zeroed<LnRowstatOut>();
     if (!h || !h->rowstat) return o;
     o.rowstat = reinterpret_cast<float2*>(h->rowstat); o.y = h->y; o.gamma = h->gamma; o.beta = h->beta;
     o.N = h->N; o.C = h->C; o.training = h->training && h->droprate > 0.f;
@@ -907,10 +804,236 @@ LnRowstatOut rowstat_out(const stgcn_ln_hook* h) {
     o.mask_from_y = hook_mask_from_y() ? 1 : 0;
     return o;
 }
+
+// the sticky error word of a workspace's chain header, once the stream has drained
+int read_chain_sticky(const char* who, const float* ws, int64_t ws_chain, uint32_t* sticky, void* stream) {
+    if (!ws || !sticky) return fail(STGCN_ERR_INVALID, "%s: NULL argument", who);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(STGCN_ERR_LAUNCH, "%s: stream synchronisation failed", who);
+    unsigned w = 0;
+    if (hipMemcpy(&w, reinterpret_cast<const unsigned*>(ws + ws_chain) + 2, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(STGCN_ERR_LAUNCH, "%s: copy failed", who);
+    *sticky = w;
+    return STGCN_OK;
+}
+// carves the ABI plan from the route: 256-byte aligned slots, in this order
+void carve_plan(const stgcn_stblock_desc* d, const BlockRoute& v, stgcn_stblock_plan* p) {
+    memset(p, 0, sizeof(*p));
+    p->T1 = v.T1; p->T2 = v.T2; p->rows1 = v.rows1; p->rows2 = v.rows2; p->NP = v.NP;
+    p->y_floats = v.rows2 * d->c2;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { int64_t at = o; o += rup(n, 64); return at; };
+    auto act = [&](int64_t n) { return v.bf16 ? (n + 1) / 2 : n; };   // 4-byte units of an activation tensor of n elements
+    p->recompute_tc1 = v.recompute_tc1;
+    p->sv_U1 = take(act(v.recompute_tc1 ? 0 : v.rows1 * d->c0));
+    p->sv_S1 = take(act(v.recompute_tc1 ? 0 : v.rows1 * d->c0));
+    p->sv_A = take(act(v.rows1 * d->c1));
+    p->sv_Xk = take((int64_t)(v.terms - 1) * act(v.rows1 * d->c1));
+    p->sv_G = take(act(v.rows1 * d->c1));
+    p->stored_US2 = v.stored_US2;
+    p->sv_U2 = take(act(v.stored_US2 ? v.rows2 * d->c2 : 0));
+    p->sv_S2 = take(act(v.stored_US2 ? v.rows2 * d->c2 : 0));
+    p->sv_mean = take(v.slabs2);
+    p->sv_rstd = take(v.slabs2);
+    p->sv_rowstat = take(2 * v.rows2);
+    p->saved_floats = o;
+    o = 0;
+    // Control words FIRST, then the packed weights: none of these offsets may depend on need_dx / training, because the pack launch that
+    // fills them may have been planned with other flags than the forward that reads them (BlockRoute: the pack needs).
+    // Header, 2 * slabs1 words that no kernel reads any more (kept so that ws_floats and every ws_* offset stay where they were -- shrinking the
+    // workspace changes the pack launch's grid and is a separate change), then the exchange words of tmp_conv2 + LayerNorm when several
+    // workgroups share a slab (64-bit, up to kTc2LnMaxPeers per slab)
+    p->chain_words = kChainHdr + 2 * v.slabs1 + 2 * kTc2LnMaxPeers * v.slabs2;
+    p->ws_chain = take(p->chain_words);
+    p->ws_W1p = take((int64_t)v.NC1 * v.KP1);
+    p->ws_W1d = take((int64_t)d->Kt * v.NC1 * v.CP_in);
+    p->ws_b1 = take(v.NC1);
+    p->ws_Wap = take((int64_t)d->c0 * d->c1);
+    p->ws_WaT = take((int64_t)v.CP1 * d->c0);
+    p->ws_ba = take(d->c1);
+    p->ws_W2p = take((int64_t)v.NC2 * v.KP2);
+    p->ws_W2d = take((int64_t)d->Kt * v.NC2 * v.CP1);
+    p->ws_b2 = take(v.NC2);
+    p->ws_W1dense = take(v.dense_W1 ? (int64_t)v.KP1 * v.NC1 : 0);
+    p->thin_tc1 = v.thin;
+    p->fused_tc2_bwd = v.tc2_bwd == BWD_FUSED;
+    p->ws_W2dense = take(v.dense_W2 ? (int64_t)v.KP2 * v.NC2 : 0);
+    p->ws_WaDense = take(v.dense_Wa_slot ? (int64_t)d->c0 * d->c1 : 0);
+    p->fused_tc1_bwd = v.tc1_bwd == BWD_FUSED;
+    p->ws_rowstat_b = take(2 * v.rows2 + 2 * v.slabs2);   // row partials, then the per-slab constants (big slabs only)
+    p->ws_dZ2 = take(act(v.rows2 * v.NC2));
+    p->ws_dYg = take(act(v.rows1 * d->c1));
+    p->ws_dA = take(act(v.rows1 * d->c1));
+    p->ws_dZ1 = take(act(v.rows1 * v.NC1));
+    p->tiled_gc = v.tiled_gc;
+    p->ws_Gk = take(v.tiled_gc ? (int64_t)v.terms * act(v.rows1 * d->c1) : 0);
+    p->ws_XT = take(v.tiled_gc && v.terms > 1 ? 2 * gc_operand_alloc(v.slabs1) * (int64_t)gc_plane_ld(v.NP) : 0);
+    p->part_floats = v.bg.total;
+    p->ws_part = take(p->part_floats);
+    p->ws_floats = o;
+}
+// check, route, plan: the head of every entry point that takes a block descriptor
+int route_and_plan(const stgcn_stblock_desc* d, BlockRoute* r, stgcn_stblock_plan* p) {
+    const int rc = check_desc(d);
+    if (rc) return rc;
+    *r = route_block(d);
+    carve_plan(d, *r, p);
+    return STGCN_OK;
+}
+// time taps of a [B][Tsrc][N][C] tensor: `rows` output rows of `taps` source steps each (dir 1: conv, -1: transposed conv), dense windows
+inline TapSrc make_taps(const float* src, int C, int taps, int N, int Tsrc, int Tdst, int dir, int64_t rows) {
+    TapSrc t = zeroed<TapSrc>();
+    t.src = src; t.C = C; t.taps = taps; t.N = N; t.Tsrc = Tsrc; t.Tdst = Tdst; t.dir = dir; t.rows = rows;
+    return t;
+}
+
+// ---- one ST block call: descriptor, route, plan, buffers, and the stage launchers that read them (the backward's: stgcn_capi_bwd.inc) ----
+struct BlockCall {
+    const stgcn_stblock_desc* d;
+    const stgcn_stblock_params* P;
+    BlockRoute r;
+    stgcn_stblock_plan pl;
+    const float* x;
+    float* saved;   // (the backward only reads it)
+    float* ws;
+    uint64_t seed, offset;
+    const uint64_t* offset_dev;
+    hipStream_t st;
+
+    int training() const { return d->training && d->droprate > 0.f; }
+    float keep_scale() const { return 1.0f / (1.0f - d->droprate); }
+    float* part() const { return ws + pl.ws_part; }
+    // the block's input as tmp_conv1 reads it: windows possibly strided, shifted by a device index or listed in a window table (TapSrc)
+    TapSrc input_taps() const {
+        TapSrc t = make_taps(x, d->c_in, d->Kt, d->N, d->T, r.T1, 1, r.rows1);
+        t.bstride = d->x_bstride; t.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); t.idx_stride = d->x_index_stride;
+        t.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
+        return t;
+    }
+
+    int launch_block_pack() {
+        PackList L;
+        if (!pack_fill_block(L, d, r, P, pl, ws, false)) return fail(STGCN_ERR_INVALID, "pack job table overflow");
+        return launch_pack_list("pack", L, st);
+    }
+    // tmp_conv1 + gate + Align on the time-stepping kernel (TC1_FWD_TSTEP)
+    int launch_tc1_fwd() {
+        Tc1FwdArgs f = zeroed<Tc1FwdArgs>();
+        f.x = x; f.Wp = ws + pl.ws_W1p; f.bias = ws + pl.ws_b1; f.WaD = ws + pl.ws_WaDense; f.ba = ws + pl.ws_ba;
+        f.U = saved + pl.sv_U1; f.S = saved + pl.sv_S1; f.A = saved + pl.sv_A;
+        f.B = d->B; f.T = d->T; f.T1 = r.T1; f.N = d->N; f.node_tiles = r.bg.node_tiles;
+        const dim3 grid((unsigned)r.tc1_fwd_wgs), blk(512);
+        const bool x6 = r.tc1_fwd_x6;
+        const size_t lds = r.tc1_fwd_lds;
+#define STGCN_TC1_FWD(CIN_)                                                                                   \
+        do {                                                                                                      \
+            if (x6 && d->act == STGCN_ACT_GLU) STGCN_LAUNCH("tconv_fwd.tc1", st, (tc1_fwd_x6_kernel<64, CIN_, 3, 0>), grid, blk, lds, f);   \
+            else if (x6) STGCN_LAUNCH("tconv_fwd.tc1", st, (tc1_fwd_x6_kernel<64, CIN_, 3, 1>), grid, blk, lds, f);      \
+            else if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (tc1_fwd_kernel<64, CIN_, 3, 0, ET>), grid, blk, lds, f);   \
+            else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (tc1_fwd_kernel<64, CIN_, 3, 1, ET>), grid, blk, lds, f);      \
+        } while (0)
+        if (d->c_in == 64) STGCN_TC1_FWD(64); else if (d->c_in == 32) STGCN_TC1_FWD(32); else STGCN_TC1_FWD(16);
+#undef STGCN_TC1_FWD
+        return STGCN_OK;
+    }
+    // the thin first layer (TC1_FWD_THIN); ride: the parked model-level pack goes out in the SAME launch (pack_thin_fwd_kernel), the layer then
+    // takes its operands straight from the parameters
+    int launch_thin_fwd(bool ride) {
+        ThinFwdArgs f = zeroed<ThinFwdArgs>();
+        f.ts = input_taps();
+        f.Wd = ws + pl.ws_W1dense; f.bias = ws + pl.ws_b1; f.Wap = ws + pl.ws_Wap; f.ba = ws + pl.ws_ba; f.A = saved + pl.sv_A;
+        const int n_thin = thin_fwd_wgs(r.rows1);
+        if (!ride) {
+            if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (thin_tc1_fwd_kernel<ET, 0>), dim3(n_thin), dim3(256), 0, f);
+            else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (thin_tc1_fwd_kernel<ET, 1>), dim3(n_thin), dim3(256), 0, f);
+            return STGCN_OK;
+        }
+        f.native = 1; f.cw = P->tc1_w; f.cb = P->tc1_b; f.aw = P->al_w; f.ab = P->al_b;
+        PackList& PL = g_pending_pack.L;
+        PL.pa.njobs = PL.nj;
+        PackSync sy{0, nullptr, 0u, 0, 0};
+        for (int k = 0; k < PL.pa.ncounters; ++k)
+            if (f.ts.idx_dev && PL.pa.cptr[k] == f.ts.idx_dev) {   // the window index of a captured step is one of the pack's counters
+                sy.on = 1; sy.idx_ptr = f.ts.idx_dev; sy.expected = (unsigned)(4 * n_thin); sy.inc = PL.pa.cinc[k]; sy.mod = PL.pa.cmod[k];
+            }
+        g_pending_pack.valid = false;
+        const dim3 gridf((unsigned)(n_thin + PL.pa.start[PL.nj]));
+        if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (pack_thin_fwd_kernel<ET, 0>), gridf, dim3(256), 0, PL.pa, f, n_thin, sy);
+        else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (pack_thin_fwd_kernel<ET, 1>), gridf, dim3(256), 0, PL.pa, f, n_thin, sy);
+        return STGCN_OK;
+    }
+    // tmp_conv1 + gate + Align on the row-tile kernels (TC1_FWD_ROWTILE)
+    int launch_rowtile_tc1_fwd() {
+        TconvFwdArgs t1 = zeroed<TconvFwdArgs>();
+        t1.ts = input_taps();
+        t1.Wp = ws + pl.ws_W1p; t1.bias = ws + pl.ws_b1; t1.KCH = r.KP1 / 16; t1.Cout = d->c0; t1.act = d->act;
+        t1.U = r.recompute_tc1 ? nullptr : saved + pl.sv_U1; t1.S = r.recompute_tc1 ? nullptr : saved + pl.sv_S1; t1.H = nullptr;
+        t1.Wap = ws + pl.ws_Wap; t1.ba = ws + pl.ws_ba; t1.A = saved + pl.sv_A; t1.c1 = d->c1;
+        return launch_tconv_fwd("tconv_fwd.tc1", t1, st);
+    }
+    // graph conv + residual + relu
+    int launch_block_gconv_fwd(const float* gso_pad) {
+        GconvFwdArgs gc = zeroed<GconvFwdArgs>();
+        gc.A = saved + pl.sv_A; gc.Lp = gso_pad; gc.W = P->gc_w; gc.bias = P->gc_b;
+        gc.Xk = saved + pl.sv_Xk; gc.G = saved + pl.sv_G;
+        gc.N = d->N; gc.NP = r.NP; gc.Ks = r.terms; gc.kipf = d->graph_conv == STGCN_GC_KIPF; gc.slabs = r.slabs1;
+        gc.XT = r.tiled_gc && r.terms > 1 ? ws + pl.ws_XT : nullptr;
+        return launch_gconv_fwd(gc, r.tiled_gc, st);
+    }
+    // tmp_conv2 + gate + LayerNorm([N, c2]) + dropout in one launch: tc2_ln_peers workgroups per (b, t2) slab
+    int launch_tc2_ln_fwd(float* y) {
+        Tc2LnFwdArgs f = zeroed<Tc2LnFwdArgs>();
+        f.G = saved + pl.sv_G; f.Wp = ws + pl.ws_W2p; f.bias = ws + pl.ws_b2; f.gamma = P->ln_w; f.beta = P->ln_b;
+        f.U = r.stored_US2 ? saved + pl.sv_U2 : nullptr; f.S = r.stored_US2 ? saved + pl.sv_S2 : nullptr;
+        f.y = y; f.mean = saved + pl.sv_mean; f.rstd = saved + pl.sv_rstd;
+        f.T1 = r.T1; f.T2 = r.T2; f.N = d->N; f.NPR = (int)rup(d->N, 16); f.act = d->act; f.training = training();
+        f.eps = d->ln_eps; f.keep_scale = keep_scale(); f.thresh = drop_thresh(d->droprate);
+        f.seed = seed; f.offset = offset; f.offset_dev = offset_dev;
+        const int pp = r.tc2_ln_peers, tpw = r.tc2_ln_tpw;
+        f.peer.words = reinterpret_cast<unsigned*>(ws + pl.ws_chain); f.peer.ncount = (int)(pp * r.slabs2); f.peer.total = (unsigned)(pp * r.slabs2);
+        f.peer.spin = g_chain_spin_ticks;
+        f.peer_slots = reinterpret_cast<unsigned long long*>(ws + pl.ws_chain + kChainHdr + 2 * r.slabs1);
+        const dim3 grid((unsigned)(r.slabs2 * pp)), blk(r.tc2_ln_threads);
+        const bool x6 = r.tc2_ln_x6;
+        const size_t lds = r.tc2_ln_lds;
+        // instances <64, Kt, tiles per wave, tile groups, peers>; x6: (2, 4, 2), (1, 4, 4) and (4, 4, 1) only
+#define STGCN_TC2LN(KT_)                                                                                  \
+        do {                                                                                                  \
+            if (x6 && pp == 2) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 2, 4, 2>), grid, blk, lds, f); \
+            else if (x6 && pp == 4) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 1, 4, 4>), grid, blk, lds, f); \
+            else if (x6) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 4, 4, 1>), grid, blk, lds, f); \
+            else if (pp == 2 && tpw == 2) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 2, 4, 2, ET>), grid, blk, lds, f); \
+            else if (pp == 4 && tpw == 1) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 1, 4, 4, ET>), grid, blk, lds, f); \
+            else if (pp == 2) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 3, 4, 2, ET>), grid, blk, lds, f); \
+            else if (pp == 4) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 2, 4, 4, ET>), grid, blk, lds, f); \
+            else if (tpw == 4) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 4, 4, 1, ET>), grid, blk, lds, f); \
+            else if (tpw == 6) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 6, 4, 1, bf16>), grid, blk, lds, f); \
+            else if (tpw == 7) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 7, 2, 1, ET>), grid, blk, lds, f); \
+            else STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 14, 2, 1, ET>), grid, blk, lds, f);           \
+        } while (0)
+        if (d->Kt == 2) STGCN_TC2LN(2); else if (d->Kt == 3) STGCN_TC2LN(3); else STGCN_TC2LN(4);
+#undef STGCN_TC2LN
+        return STGCN_OK;
+    }
+    // the same on the stage-per-launch kernels: tmp_conv2 + gate, then LayerNorm + dropout
+    int launch_staged_tc2_ln_fwd(float* y) {
+        TconvFwdArgs t2 = zeroed<TconvFwdArgs>();
+        t2.ts = make_taps(saved + pl.sv_G, d->c1, d->Kt, d->N, r.T1, r.T2, 1, r.rows2);
+        t2.Wp = ws + pl.ws_W2p; t2.bias = ws + pl.ws_b2; t2.KCH = r.KP2 / 16; t2.Cout = d->c2; t2.act = d->act;
+        t2.U = saved + pl.sv_U2; t2.S = saved + pl.sv_S2; t2.rowstat = reinterpret_cast<float2*>(saved + pl.sv_rowstat);
+        const int rc = launch_tconv_fwd("tconv_fwd.tc2", t2, st);
+        if (rc) return rc;
+        LnFwdArgs ln = zeroed<LnFwdArgs>();
+        ln.U = saved + pl.sv_U2; ln.S = saved + pl.sv_S2; ln.gamma = P->ln_w; ln.beta = P->ln_b; ln.y = y;
+        ln.mean = saved + pl.sv_mean; ln.rstd = saved + pl.sv_rstd; ln.rowstat = reinterpret_cast<const float2*>(saved + pl.sv_rowstat);
+        ln.n = d->N * d->c2; ln.N = d->N; ln.C = d->c2; ln.act = d->act; ln.training = training();
+        ln.eps = d->ln_eps; ln.keep_scale = keep_scale(); ln.thresh = drop_thresh(d->droprate);
+        ln.seed = seed; ln.offset = offset; ln.offset_dev = offset_dev;
+        return launch_ln_fwd("ln_fwd", ln, r.slabs2, st);
+    }
+};
 }  // namespace
 
-extern "C" {
-
+// ---- entry points (C linkage from their declarations in include/stgcn_hip.h) ---------------------------------------------------------------
 int stgcn_version(void) { return STGCN_ABI_VERSION; }
 const char* stgcn_backend(void) { return STGCN_BACKEND_NAME; }
 const char* stgcn_last_error(void) { return g_err; }
@@ -951,127 +1074,32 @@ int stgcn_profile_collect(char* buf, size_t cap) {
 }
 
 int stgcn_stblock_plan_query(const stgcn_stblock_desc* d, stgcn_stblock_plan* p) {
-    int rc = check_desc(d);
+    const int rc = check_desc(d);
     if (rc) return rc;
     if (!p) return fail(STGCN_ERR_INVALID, "plan is NULL");
-    const Derived v = derive(d);
-    memset(p, 0, sizeof(*p));
-    p->T1 = v.T1; p->T2 = v.T2; p->rows1 = v.rows1; p->rows2 = v.rows2; p->NP = v.NP;
-    p->y_floats = v.rows2 * d->c2;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { int64_t at = o; o += rup(n, 64); return at; };   // 256-byte aligned carve
-    const bool bf = d->dtype == STGCN_DTYPE_BF16;
-    auto act = [&](int64_t n) { return bf ? (n + 1) / 2 : n; };   // 4-byte units of an activation tensor of n elements
-    p->recompute_tc1 = (d->Kt * d->c_in <= 16) ? 1 : 0;   // K <= 16: recomputing Z in backward beats storing 2 x rows1 x c0
-    p->sv_U1 = take(act(p->recompute_tc1 ? 0 : v.rows1 * d->c0));
-    p->sv_S1 = take(act(p->recompute_tc1 ? 0 : v.rows1 * d->c0));
-    p->sv_A = take(act(v.rows1 * d->c1));
-    p->sv_Xk = take((int64_t)(v.terms - 1) * act(v.rows1 * d->c1));
-    p->sv_G = take(act(v.rows1 * d->c1));
-    const BwdGeom bgs = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
-    p->stored_US2 = (!tc2_ln_fwd_fused_ok(d->c1, d->c2, d->Kt, d->N) || !bgs.k1 || g_debug_stages || !tc2_recompute(bf)) ? 1 : 0;
-    p->sv_U2 = take(act(p->stored_US2 ? v.rows2 * d->c2 : 0));
-    p->sv_S2 = take(act(p->stored_US2 ? v.rows2 * d->c2 : 0));
-    p->sv_mean = take(v.slabs2);
-    p->sv_rstd = take(v.slabs2);
-    p->sv_rowstat = take(2 * v.rows2);
-    p->saved_floats = o;
-    o = 0;
-    // control words of the chained launches FIRST: their offset must not depend on need_dx / training, because the pack launch that zeroes
-    // them may have been planned with other flags than the forward that uses them (stgcn_prepack packs a whole model with need_dx = 1)
-    // control words of the forward: header, 2 * slabs1 words that no kernel reads any more (the arrival counters of the removed chained
-    // forward; kept so that ws_floats and every ws_* offset stay where they were -- shrinking the workspace is a separate change), then the
-    // exchange words of tmp_conv2 + LayerNorm when several workgroups share a slab (64-bit, up to kTc2LnMaxPeers per slab)
-    p->chain_words = kChainHdr + 2 * v.slabs1 + 2 * kTc2LnMaxPeers * v.slabs2;
-    p->ws_chain = take(p->chain_words);
-    p->ws_W1p = take((int64_t)v.NC1 * v.KP1);
-    p->ws_W1d = take((int64_t)d->Kt * v.NC1 * v.CP_in);
-    p->ws_b1 = take(v.NC1);
-    p->ws_Wap = take((int64_t)d->c0 * d->c1);
-    p->ws_WaT = take((int64_t)v.CP1 * d->c0);
-    p->ws_ba = take(d->c1);
-    p->ws_W2p = take((int64_t)v.NC2 * v.KP2);
-    p->ws_W2d = take((int64_t)d->Kt * v.NC2 * v.CP1);
-    p->ws_b2 = take(v.NC2);
-    const bool k3s = (tc1_bwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt) || tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt)) && (d->Kt * d->c_in > 4);
-    p->ws_W1dense = take((p->recompute_tc1 || k3s) ? (int64_t)v.KP1 * v.NC1 : 0);
-    const BwdGeom bgq = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
-    p->thin_tc1 = bgq.thin;
-    p->fused_tc2_bwd = bgq.k1;
-    p->ws_W2dense = take(bgq.k1 ? (int64_t)v.KP2 * v.NC2 : 0);
-    p->ws_WaDense = take((p->thin_tc1 || k3s) ? (int64_t)d->c0 * d->c1 : 0);
-    p->fused_tc1_bwd = bgq.k3;
-    p->ws_rowstat_b = take(2 * v.rows2 + 2 * v.slabs2);   // row partials, then the per-slab constants (big slabs only)
-    p->ws_dZ2 = take(act(v.rows2 * v.NC2));
-    p->ws_dYg = take(act(v.rows1 * d->c1));
-    p->ws_dA = take(act(v.rows1 * d->c1));
-    p->ws_dZ1 = take(act(v.rows1 * v.NC1));
-    p->tiled_gc = v.tiled;
-    p->ws_Gk = take(v.tiled ? (int64_t)v.terms * act(v.rows1 * d->c1) : 0);
-    p->ws_XT = take(v.tiled && v.terms > 1 ? 2 * gc_operand_alloc(v.slabs1) * (int64_t)gc_plane_ld(v.NP) : 0);
-    p->part_floats = bwd_partial_floats(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
-    p->ws_part = take(p->part_floats);
-    p->ws_floats = o;
+    carve_plan(d, route_block(d), p);
     return STGCN_OK;
 }
 
-int stgcn_set_debug_stages(int32_t on) {
-    const int prev = g_debug_stages;
-    if (on == 0 || on == 1) g_debug_stages = on;
+// stgcn_set_*: a valid value replaces the knob; the previous value is returned either way
+template <typename T>
+T set_knob(T& knob, T v, bool valid) {
+    const T prev = knob;
+    if (valid) knob = v;
     return prev;
 }
-
+int stgcn_set_debug_stages(int32_t on) { return set_knob(g_debug_stages, on, on == 0 || on == 1); }
+int stgcn_set_tc1_bwd_wgs(int32_t n) { return set_knob(g_tc1_bwd_wgs, n, n >= 0); }
+int stgcn_set_tc2ln_peers(int32_t n) { return set_knob(g_tc2ln_peers, n, n == 0 || n == 1 || n == 2 || n == 4); }
+int stgcn_set_gc_tiled_min_nodes(int32_t n) { return set_knob(g_gc_tiled_min_n, n, n >= 1); }
+int stgcn_set_gc_ld_pad(int32_t pad) { return set_knob(g_gc_ld_pad, pad, pad >= 0 && pad <= 65536 && (pad & 7) == 0); }
+int stgcn_set_gemm_big_nt(int32_t nt) { return set_knob(g_gemm_big_nt, nt, nt == 0 || nt == 4 || nt == 5 || nt == 6 || nt == 8 || nt == 10); }
+int stgcn_set_gc_precision(int32_t mode) { return set_knob(g_gc_precision, mode, mode >= 0 && mode <= 2); }
+int stgcn_set_bwd_precision(int32_t mode) { return set_knob(g_bwd_precision, mode, mode >= 0 && mode <= 1); }
+int stgcn_set_slab_gc_precision(int32_t mode) { return set_knob(g_slab_gc_precision, mode, mode >= 0 && mode <= 1); }
 int64_t stgcn_set_chain_spin_ticks(int64_t ticks) {
     if (ticks == 0) return g_chain_spin_ticks.load();
     return g_chain_spin_ticks.exchange(ticks);
-}
-
-int stgcn_set_tc1_bwd_wgs(int32_t n) {
-    const int prev = g_tc1_bwd_wgs;
-    if (n >= 0) g_tc1_bwd_wgs = n;
-    return prev;
-}
-
-int stgcn_set_tc2ln_peers(int32_t n) {
-    const int prev = g_tc2ln_peers;
-    if (n == 0 || n == 1 || n == 2 || n == 4) g_tc2ln_peers = n;
-    return prev;
-}
-
-int stgcn_set_gc_tiled_min_nodes(int32_t n) {
-    const int prev = g_gc_tiled_min_n;
-    if (n >= 1) g_gc_tiled_min_n = n;
-    return prev;
-}
-
-int stgcn_set_gc_ld_pad(int32_t pad) {
-    const int prev = g_gc_ld_pad;
-    if (pad >= 0 && pad <= 65536 && (pad & 7) == 0) g_gc_ld_pad = pad;
-    return prev;
-}
-
-int stgcn_set_gemm_big_nt(int32_t nt) {
-    const int prev = g_gemm_big_nt;
-    if (nt == 0 || nt == 4 || nt == 5 || nt == 6 || nt == 8 || nt == 10) g_gemm_big_nt = nt;
-    return prev;
-}
-
-int stgcn_set_gc_precision(int32_t mode) {
-    const int prev = g_gc_precision;
-    if (mode >= 0 && mode <= 2) g_gc_precision = mode;
-    return prev;
-}
-
-int stgcn_set_bwd_precision(int32_t mode) {
-    const int prev = g_bwd_precision;
-    if (mode >= 0 && mode <= 1) g_bwd_precision = mode;
-    return prev;
-}
-
-int stgcn_set_slab_gc_precision(int32_t mode) {
-    const int prev = g_slab_gc_precision;
-    if (mode >= 0 && mode <= 1) g_slab_gc_precision = mode;
-    return prev;
 }
 
 int stgcn_gso_layout(int32_t N, int32_t terms, int64_t* NP, int64_t* mats, int64_t* scratch_mats, int32_t* tiled) {
@@ -1151,21 +1179,15 @@ int stgcn_stblock_ln_hook(const stgcn_stblock_desc* d, const stgcn_stblock_param
 int stgcn_stblock_chain_status(const stgcn_stblock_desc* d, const float* ws, uint32_t* sticky, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     stgcn_stblock_plan pl;
-    int rc = stgcn_stblock_plan_query(d, &pl);
+    const int rc = stgcn_stblock_plan_query(d, &pl);
     if (rc) return rc;
-    if (!ws || !sticky) return fail(STGCN_ERR_INVALID, "stgcn_stblock_chain_status: NULL argument");
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(STGCN_ERR_LAUNCH, "stgcn_stblock_chain_status: stream synchronisation failed");
-    unsigned w = 0;
-    if (hipMemcpy(&w, reinterpret_cast<const unsigned*>(ws + pl.ws_chain) + 2, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(STGCN_ERR_LAUNCH, "stgcn_stblock_chain_status: copy failed");
-    *sticky = w;
-    return STGCN_OK;
+    return read_chain_sticky("stgcn_stblock_chain_status", ws, pl.ws_chain, sticky, stream);
 }
 
 int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_params* P, const float* x, const float* gso_pad, float* y,
                           float* saved, float* ws, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream) {
-    stgcn_stblock_plan pl;
-    int rc = stgcn_stblock_plan_query(d, &pl);
+    BlockCall c{d, P, {}, {}, x, saved, ws, seed, offset, offset_dev, (hipStream_t)stream};
+    int rc = route_and_plan(d, &c.r, &c.pl);
     if (rc) return rc;
     if (!P || !x || !gso_pad || !y || !saved || !ws) return fail(STGCN_ERR_INVALID, "stgcn_stblock_forward: NULL buffer");
     if (!P->tc1_w || !P->tc1_b || !P->gc_w || !P->tc2_w || !P->tc2_b || !P->ln_w || !P->ln_b)
@@ -1173,162 +1195,26 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
     if (d->c_in > d->c0 && !P->tc1_aw) return fail(STGCN_ERR_INVALID, "tc1_aw required when c_in > c0");
     if (d->c0 > d->c1 && !P->al_w) return fail(STGCN_ERR_INVALID, "al_w required when c0 > c1");
     if (d->c1 > d->c2 && !P->tc2_aw) return fail(STGCN_ERR_INVALID, "tc2_aw required when c1 > c2");
-    const Derived v = derive(d);
-    hipStream_t st = (hipStream_t)stream;
     g_prof_tag = d->reserved;
-    g_bf16 = d->dtype == STGCN_DTYPE_BF16;
+    g_bf16 = c.r.bf16;
 
-    // a parked model-level pack (stgcn_prepack): fused with this block's thin first layer when that is what comes next, else launched now
-    const bool thin_first = pl.thin_tc1 && thin_wave_tiles() &&
-                            !(!pl.recompute_tc1 && !d->x_bstride && !d->x_index_dev && tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt));
-    const bool fuse_pack = g_pending_pack.valid && d->prepacked && thin_first && g_pending_pack.st == st &&
-                           d->c0 == 64 && d->c1 == 16 && d->c_in < d->c0;
-    if (!fuse_pack) STGCN_FLUSH_PENDING_PACK();
-    rc = d->prepacked ? STGCN_OK : launch_pack(d, P, pl, ws, st);
+    // a parked model-level pack (stgcn_prepack) rides on this block's thin first layer when that is what comes next, else it is launched now
+    // (the thin layer has c0 64, c1 16 and c_in <= 4: all that pack_thin_fwd_kernel asks of the shape)
+    const bool ride = g_pending_pack.valid && d->prepacked && c.r.tc1_fwd == TC1_FWD_THIN && g_pending_pack.st == c.st;
+    if (!ride) STGCN_FLUSH_PENDING_PACK();
+    if (!d->prepacked) rc = c.launch_block_pack();
     if (rc) return rc;
 
-    // ---- tmp_conv1 + GLU + Align(c0 -> c1) -----------------------------------------------------
-    if (!pl.recompute_tc1 && !d->x_bstride && !d->x_index_dev && tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt)) {
-        // time-stepping kernel: weights stationary in registers, every input tile read once (stgcn_kernels_tstep.hip.h)
-        Tc1FwdArgs f;
-        memset(&f, 0, sizeof(f));
-        f.x = x; f.Wp = ws + pl.ws_W1p; f.bias = ws + pl.ws_b1; f.WaD = ws + pl.ws_WaDense; f.ba = ws + pl.ws_ba;
-        f.U = saved + pl.sv_U1; f.S = saved + pl.sv_S1; f.A = saved + pl.sv_A;
-        f.B = d->B; f.T = d->T; f.T1 = v.T1; f.N = d->N; f.node_tiles = (d->N + 15) / 16;
-        const long items = (long)d->B * f.node_tiles;
-        // workgroups per CU: one for fp32 (its steps are bound by the fp32 matrix pipe: a second chain on the CU made it 12 % slower), two for
-        // bf16 activations (8 x cheaper MFMAs leave a latency chain: C3 34.2 -> 27.1 us, r3-31)
-        const int fwd_per_cu = g_bf16 ? 2 : 1;
-        const long want = (long)device_cus() * fwd_per_cu;                                    // (stgcn_set_tc1_bwd_wgs overrides the CU count in tests)
-        const long by_steps = items * (long)v.T1 / tc1_min_steps(), most = items > by_steps ? items : by_steps;   // (small batches: ranges cut inside items)
-        const dim3 grid((unsigned)(most < want ? most : want)), blk(512);                     // equal (item, step) ranges, one workgroup per CU
-        const bool x6 = mfma_x6() && !g_bf16;
-        const size_t lds = tc1_fwd_lds_bytes(d->c_in, d->Kt, x6);
-#define STGCN_TC1_FWD(CIN_)                                                                                   \
-        do {                                                                                                  \
-            if (x6 && d->act == STGCN_ACT_GLU) STGCN_LAUNCH("tconv_fwd.tc1", st, (tc1_fwd_x6_kernel<64, CIN_, 3, 0>), grid, blk, lds, f);   \
-            else if (x6) STGCN_LAUNCH("tconv_fwd.tc1", st, (tc1_fwd_x6_kernel<64, CIN_, 3, 1>), grid, blk, lds, f);      \
-            else if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (tc1_fwd_kernel<64, CIN_, 3, 0, ET>), grid, blk, lds, f);   \
-            else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (tc1_fwd_kernel<64, CIN_, 3, 1, ET>), grid, blk, lds, f);      \
-        } while (0)
-        if (d->c_in == 64) STGCN_TC1_FWD(64); else if (d->c_in == 32) STGCN_TC1_FWD(32); else STGCN_TC1_FWD(16);
-#undef STGCN_TC1_FWD
-    } else if (pl.thin_tc1 && thin_wave_tiles()) {
-        // thin first layer (K = Kt * c_in <= 4): one wave per 16-row tile, no LDS, no barrier (stgcn_kernels_thin.hip.h)
-        ThinFwdArgs f;
-        memset(&f, 0, sizeof(f));
-        f.ts.src = x; f.ts.C = d->c_in; f.ts.taps = d->Kt; f.ts.N = d->N; f.ts.Tsrc = d->T; f.ts.Tdst = v.T1; f.ts.dir = 1; f.ts.rows = v.rows1;
-        f.ts.bstride = d->x_bstride; f.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); f.ts.idx_stride = d->x_index_stride; f.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
-        f.Wd = ws + pl.ws_W1dense; f.bias = ws + pl.ws_b1; f.Wap = ws + pl.ws_Wap; f.ba = ws + pl.ws_ba; f.A = saved + pl.sv_A;
-        if (fuse_pack) {
-            // ONE launch: the layer (operands straight from the parameters) + the parked pack jobs (pack_thin_fwd_kernel)
-            f.native = 1; f.cw = P->tc1_w; f.cb = P->tc1_b; f.aw = P->al_w; f.ab = P->al_b;
-            PackList& PL = g_pending_pack.L;
-            PL.pa.njobs = PL.nj;
-            const int n_thin = thin_fwd_wgs(v.rows1);
-            PackSync sy{0, nullptr, 0u, 0, 0};
-            for (int k = 0; k < PL.pa.ncounters; ++k)
-                if (f.ts.idx_dev && PL.pa.cptr[k] == f.ts.idx_dev) {   // the window index of a captured step is one of the pack's counters
-                    sy.on = 1; sy.idx_ptr = f.ts.idx_dev; sy.expected = (unsigned)(4 * n_thin); sy.inc = PL.pa.cinc[k]; sy.mod = PL.pa.cmod[k];
-                }
-            g_pending_pack.valid = false;
-            const dim3 gridf((unsigned)(n_thin + PL.pa.start[PL.nj]));
-            if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (pack_thin_fwd_kernel<ET, 0>), gridf, dim3(256), 0, PL.pa, f, n_thin, sy);
-            else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (pack_thin_fwd_kernel<ET, 1>), gridf, dim3(256), 0, PL.pa, f, n_thin, sy);
-        } else
-        if (d->act == STGCN_ACT_GLU) STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (thin_tc1_fwd_kernel<ET, 0>), dim3(thin_fwd_wgs(v.rows1)), dim3(256), 0, f);
-        else STGCN_LAUNCH_ET("tconv_fwd.tc1", st, (thin_tc1_fwd_kernel<ET, 1>), dim3(thin_fwd_wgs(v.rows1)), dim3(256), 0, f);
-    } else
-    {
-        TconvFwdArgs t1;
-        memset(&t1, 0, sizeof(t1));
-        t1.ts.src = x; t1.ts.C = d->c_in; t1.ts.taps = d->Kt; t1.ts.N = d->N; t1.ts.Tsrc = d->T; t1.ts.Tdst = v.T1; t1.ts.dir = 1;
-        t1.ts.rows = v.rows1;
-        t1.ts.bstride = d->x_bstride; t1.ts.idx_dev = reinterpret_cast<const long*>(d->x_index_dev); t1.ts.idx_stride = d->x_index_stride; t1.ts.win_tab = reinterpret_cast<const long*>(d->x_window_dev);
-        t1.Wp = ws + pl.ws_W1p; t1.bias = ws + pl.ws_b1; t1.KCH = v.KP1 / 16; t1.Cout = d->c0; t1.act = d->act;
-        t1.U = pl.recompute_tc1 ? nullptr : saved + pl.sv_U1; t1.S = pl.recompute_tc1 ? nullptr : saved + pl.sv_S1; t1.H = nullptr;
-        t1.Wap = ws + pl.ws_Wap; t1.ba = ws + pl.ws_ba; t1.A = saved + pl.sv_A; t1.c1 = d->c1;
-        rc = launch_tconv_fwd("tconv_fwd.tc1", t1, st);
-        if (rc) return rc;
+    switch (c.r.tc1_fwd) {
+        case TC1_FWD_TSTEP: rc = c.launch_tc1_fwd(); break;
+        case TC1_FWD_THIN: rc = c.launch_thin_fwd(ride); break;
+        case TC1_FWD_ROWTILE: rc = c.launch_rowtile_tc1_fwd(); break;
     }
-
-    // ---- graph conv + residual + relu -----------------------------------------------------------
-    GconvFwdArgs gc;
-    memset(&gc, 0, sizeof(gc));
-    gc.A = saved + pl.sv_A; gc.Lp = gso_pad; gc.W = P->gc_w; gc.bias = P->gc_b;
-    gc.Xk = saved + pl.sv_Xk; gc.G = saved + pl.sv_G;
-    gc.N = d->N; gc.NP = v.NP; gc.Ks = v.terms; gc.kipf = d->graph_conv == STGCN_GC_KIPF; gc.slabs = v.slabs1;
-    gc.XT = pl.tiled_gc && v.terms > 1 ? ws + pl.ws_XT : nullptr;
-    rc = launch_gconv_fwd(gc, st);
     if (rc) return rc;
-
-    if (tc2_ln_fwd_fused_ok(d->c1, d->c2, d->Kt, d->N)) {
-        // ---- tmp_conv2 + GLU + LayerNorm([N, c2]) + dropout: one workgroup per (b, t2) slab ------------------------------------
-        Tc2LnFwdArgs f;
-        memset(&f, 0, sizeof(f));
-        f.G = saved + pl.sv_G; f.Wp = ws + pl.ws_W2p; f.bias = ws + pl.ws_b2; f.gamma = P->ln_w; f.beta = P->ln_b;
-        f.U = pl.stored_US2 ? saved + pl.sv_U2 : nullptr; f.S = pl.stored_US2 ? saved + pl.sv_S2 : nullptr;
-        f.y = y; f.mean = saved + pl.sv_mean; f.rstd = saved + pl.sv_rstd;
-        f.T1 = v.T1; f.T2 = v.T2; f.N = d->N; f.NPR = (int)rup(d->N, 16); f.act = d->act; f.training = d->training && d->droprate > 0.f;
-        f.eps = d->ln_eps; f.keep_scale = 1.0f / (1.0f - d->droprate); f.thresh = drop_thresh(d->droprate);
-        f.seed = seed; f.offset = offset; f.offset_dev = offset_dev;
-        const bool x6 = mfma_x6() && !g_bf16 && d->N <= 256 && v.slabs2 <= 2L * device_cus() && d->Kt <= 3;   // "bf16x6" products: the 16-wave forms of up to 256 nodes (4 taps: 8 weight plane triples spill)
-        const size_t lds = tc2_ln_fwd_lds_bytes(d->Kt, d->N, x6);
-        // workgroups per slab (round 6): a slab is one serial chain of ~15 us whatever the batch, so a launch that leaves compute units idle
-        // (block 1 of C2: 128 slabs; every small batch) cuts the slab's node tiles over PP workgroups that exchange their statistics
-        const int pp = tc2_ln_peers(d->N, v.slabs2);
-        f.peer.words = reinterpret_cast<unsigned*>(ws + pl.ws_chain); f.peer.ncount = (int)(pp * v.slabs2); f.peer.total = (unsigned)(pp * v.slabs2);
-        f.peer.spin = g_chain_spin_ticks;
-        f.peer_slots = reinterpret_cast<unsigned long long*>(ws + pl.ws_chain + kChainHdr + 2 * v.slabs1);
-        const dim3 grid((unsigned)(v.slabs2 * pp));
-        // 16 waves (4 tile groups) when the grid leaves room for it: at most ~2 workgroups per CU (measured at C2: 25.8 -> ?? us)
-        // (up to 384 nodes = 6 tiles per wave of a four-group workgroup: C3's 325-node slabs ran on 8 waves, one workgroup per CU, two rounds)
-        // (the 6-tile form only for bf16 activations: with fp32 fragments it needs more than the 128 registers of a 16-wave workgroup)
-        const bool wide = d->N <= (g_bf16 ? 384 : 256) && v.slabs2 <= 2L * device_cus();
-        const bool small = d->N <= 224;   // 7 row tiles per wave of a two-group workgroup
-#define STGCN_TC2LN(KT_)                                                                                  \
-        do {                                                                                              \
-            if (x6 && pp == 2) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 2, 4, 2>), grid, dim3(1024), lds, f); \
-            else if (x6 && pp == 4) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 1, 4, 4>), grid, dim3(1024), lds, f); \
-            else if (x6 && wide) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_x6_kernel<64, (KT_ <= 3 ? KT_ : 3), 4, 4, 1>), grid, dim3(1024), lds, f); \
-            else if (pp == 2 && d->N <= 256) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 2, 4, 2, ET>), grid, dim3(1024), lds, f); \
-            else if (pp == 4 && d->N <= 256) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 1, 4, 4, ET>), grid, dim3(1024), lds, f); \
-            else if (pp == 2) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 3, 4, 2, ET>), grid, dim3(1024), lds, f); \
-            else if (pp == 4) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 2, 4, 4, ET>), grid, dim3(1024), lds, f); \
-            else if (wide && d->N <= 256) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 4, 4, 1, ET>), grid, dim3(1024), lds, f); \
-            else if (wide) STGCN_LAUNCH("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 6, 4, 1, bf16>), grid, dim3(1024), lds, f); \
-            else if (small) STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 7, 2, 1, ET>), grid, dim3(512), lds, f); \
-            else STGCN_LAUNCH_ET("tc2_ln_fwd", st, (tc2_ln_fwd_kernel<64, KT_, 14, 2, 1, ET>), grid, dim3(512), lds, f);           \
-        } while (0)
-        if (d->Kt == 2) STGCN_TC2LN(2); else if (d->Kt == 3) STGCN_TC2LN(3); else STGCN_TC2LN(4);
-#undef STGCN_TC2LN
-        return STGCN_OK;
-    }
-
-    // ---- tmp_conv2 + GLU ---------------------------------------------------------------------------
-    TconvFwdArgs t2;
-    memset(&t2, 0, sizeof(t2));
-    t2.ts.src = saved + pl.sv_G; t2.ts.C = d->c1; t2.ts.taps = d->Kt; t2.ts.N = d->N; t2.ts.Tsrc = v.T1; t2.ts.Tdst = v.T2; t2.ts.dir = 1;
-    t2.ts.rows = v.rows2;
-    t2.Wp = ws + pl.ws_W2p; t2.bias = ws + pl.ws_b2; t2.KCH = v.KP2 / 16; t2.Cout = d->c2; t2.act = d->act;
-    t2.U = saved + pl.sv_U2; t2.S = saved + pl.sv_S2; t2.rowstat = reinterpret_cast<float2*>(saved + pl.sv_rowstat);
-    rc = launch_tconv_fwd("tconv_fwd.tc2", t2, st);
+    rc = c.launch_block_gconv_fwd(gso_pad);
     if (rc) return rc;
-
-    // ---- LayerNorm([N, c2]) + dropout ----------------------------------------------------------------
-    LnFwdArgs ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.U = saved + pl.sv_U2; ln.S = saved + pl.sv_S2; ln.gamma = P->ln_w; ln.beta = P->ln_b; ln.y = y;
-    ln.mean = saved + pl.sv_mean; ln.rstd = saved + pl.sv_rstd; ln.rowstat = reinterpret_cast<const float2*>(saved + pl.sv_rowstat);
-    ln.n = d->N * d->c2; ln.N = d->N; ln.C = d->c2; ln.act = d->act; ln.training = d->training && d->droprate > 0.f;
-    ln.eps = d->ln_eps; ln.keep_scale = 1.0f / (1.0f - d->droprate); ln.thresh = drop_thresh(d->droprate);
-    ln.seed = seed; ln.offset = offset; ln.offset_dev = offset_dev;
-    rc = launch_ln_fwd("ln_fwd", ln, v.slabs2, st);
-    if (rc) return rc;
-    return STGCN_OK;
+    return c.r.tc2_ln_fused ? c.launch_tc2_ln_fwd(y) : c.launch_staged_tc2_ln_fwd(y);
 }
 
 #include "stgcn_capi_bwd.inc"
 #include "stgcn_capi_head.inc"
-
-}  // extern "C"

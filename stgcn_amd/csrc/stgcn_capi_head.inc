@@ -1,5 +1,6 @@
-// Output-head entry points (included inside the extern "C" block of stgcn_capi.hip).
+// Output head, model-level pack, gradient flush, optimizers and evaluation: helpers, then the entry points (included by stgcn_capi.hip).
 
+namespace {
 struct HeadGeom {
     int T1, NC, KP, KCH, CPin, ln_spg, ln_sg, fc_wgs;
     int dense_bwd;        // T1 == 1: the transposed conv is ONE dense GEMM dZ[B*N x NC] @ [NC x Ko*c_in] (tconv_fwd4_kernel<PLAIN>)
@@ -9,7 +10,7 @@ struct HeadGeom {
     long off_ln_g, off_ln_b, off_fc, total;
 };
 
-static int head_check(const stgcn_outblock_desc* d) {
+int head_check(const stgcn_outblock_desc* d) {
     if (!d) return fail(STGCN_ERR_INVALID, "desc is NULL");
     if (d->B < 1 || d->T < 1 || d->N < 1 || d->c_in < 1 || d->Ko < 1) return fail(STGCN_ERR_INVALID, "B/T/N/c_in/Ko must be positive");
     if (d->T < d->Ko) return fail(STGCN_ERR_INVALID, "T=%d shorter than Ko=%d", d->T, d->Ko);
@@ -23,17 +24,14 @@ static int head_check(const stgcn_outblock_desc* d) {
     return STGCN_OK;
 }
 
-static HeadGeom head_geom(const stgcn_outblock_desc* d) {
+HeadGeom head_geom(const stgcn_outblock_desc* d) {
     HeadGeom g;
     g.T1 = d->T - d->Ko + 1;
     g.NC = 2 * d->c0;
     g.KP = (int)rup((int64_t)d->Ko * d->c_in, 16);
     g.KCH = g.KP / 16;
     g.CPin = (int)rup(d->c_in, 16);
-    {
-        static const int off = getenv("STGCN_TCONV4") ? atoi(getenv("STGCN_TCONV4")) == 0 : 0;
-        g.dense_bwd = !off && g.T1 == 1 && g.NC == 256 && d->Ko * d->c_in == 256 && (d->c_in & 3) == 0;
-    }
+    g.dense_bwd = !tconv4_off() && g.T1 == 1 && g.NC == 256 && d->Ko * d->c_in == 256 && (d->c_in & 3) == 0;
     g.rows = (int64_t)d->B * g.T1 * d->N;
     g.rows_in = (int64_t)d->B * d->T * d->N;
     g.slabs = (int64_t)d->B * g.T1;
@@ -75,7 +73,7 @@ static HeadGeom head_geom(const stgcn_outblock_desc* d) {
     return g;
 }
 
-static void reduce_jobs_head(ReduceList& L, const stgcn_outblock_desc* d, const HeadGeom& g, const float* part, const float* dyln,
+void reduce_jobs_head(ReduceList& L, const stgcn_outblock_desc* d, const HeadGeom& g, const float* part, const float* dyln,
                              const stgcn_outblock_grads* G) {
     {
         const WgradGeom& w = g.wc;
@@ -105,6 +103,254 @@ static void reduce_jobs_head(ReduceList& L, const stgcn_outblock_desc* d, const 
     if (g.fused_ln_bwd && d->dtype == STGCN_DTYPE_F32) L.add_flat(G->ln_b, dyln, g.ln_sg, n, n);      // dbeta[n][c] = sum over slabs of dy: straight from the (fp32) gradient tensor
     else L.add_flat(G->ln_b, part + g.off_ln_b, g.ln_sg, n, n);
 }
+
+bool pack_fill_head(PackList& L, const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const stgcn_outblock_plan& pl, float* ws,
+                    bool all) {
+    const HeadGeom g = head_geom(d);
+    bool ok = true;
+    ok &= L.add(PK_TCONV_FWD, g.NC * g.KP, ws + pl.ws_Wp, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, g.KCH);
+    if (d->need_dx || all) {
+        if (g.dense_bwd)   // same footprint (NC x Ko*c_in floats), K = NC
+            ok &= L.add(PK_TCONV_BWDT, g.NC * d->Ko * d->c_in, ws + pl.ws_Wd, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, g.NC / 16);
+        else
+            ok &= L.add(PK_TCONV_BWD, d->Ko * g.NC * g.CPin, ws + pl.ws_Wd, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko,
+                        d->Ko * g.NC / 16);
+    }
+    ok &= L.add(PK_TCONV_BIAS, g.NC, ws + pl.ws_b, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, 0);
+    ok &= L.add(PK_LIN_FWD, d->c0 * d->c1, ws + pl.ws_W1p, P->fc1_w, nullptr, nullptr, nullptr, d->c0, d->c1, 1, d->c0 / 16);
+    ok &= L.add(PK_LIN_BWD, d->c1 * d->c0, ws + pl.ws_W1d, P->fc1_w, nullptr, nullptr, nullptr, d->c0, d->c1, 1, d->c1 / 16);
+    ok &= L.add(PK_ZERO, (int)pl.chain_words, ws + pl.ws_chain, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0);   // control words of the fused forward
+    return ok;
+}
+
+int prepack_impl(int32_t n_blocks, const stgcn_prepack_block* blocks, const stgcn_outblock_desc* hd, const stgcn_outblock_params* hp,
+                 float* hws, int32_t n_counters, const stgcn_step_counter* counters, void* stream, bool park) {
+    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "stgcn_prepack: bad block list");
+    if (n_counters < 0 || n_counters > kMaxStepCounters || (n_counters > 0 && !counters))
+        return fail(STGCN_ERR_INVALID, "stgcn_prepack: at most %d step counters", kMaxStepCounters);
+    STGCN_FLUSH_PENDING_PACK();   // (a pack parked by an earlier call that no forward picked up)
+    // one launch for the whole model while the job table holds it; models with many ST blocks (Kt = 2, n_his = 12 allows 5) spill into
+    // further launches (the step counters ride on the first one)
+    g_prof_tag = 0;
+    PackList L;
+    L.pa.ncounters = n_counters;
+    for (int k = 0; k < n_counters; ++k) {
+        if (!counters[k].ptr) return fail(STGCN_ERR_INVALID, "stgcn_prepack: NULL step counter %d", k);
+        L.pa.cptr[k] = reinterpret_cast<long*>(counters[k].ptr); L.pa.cinc[k] = (long)counters[k].inc; L.pa.cmod[k] = (long)counters[k].mod;
+    }
+    auto flush_list = [&]() -> int {
+        const int rc = launch_pack_list("prepack", L, (hipStream_t)stream);
+        L = PackList();
+        return rc;
+    };
+    // appends one module's jobs; a module that does not fit behind the jobs collected so far starts a new launch
+    auto append = [&](auto&& fill) -> int {
+        PackList trial = L;
+        if (!fill(trial)) {
+            if (L.nj == 0) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_prepack: one module needs more than %d pack jobs", kMaxPackJobs);
+            const int rc = flush_list();
+            if (rc) return rc;
+            trial = L;
+            if (!fill(trial)) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_prepack: pack job table overflow");
+        }
+        L = trial;
+        return STGCN_OK;
+    };
+    for (int i = 0; i < n_blocks; ++i) {
+        const stgcn_prepack_block& b = blocks[i];
+        if (!b.desc || !b.params || !b.ws) return fail(STGCN_ERR_INVALID, "stgcn_prepack: NULL entry in block %d", i);
+        BlockRoute r;
+        stgcn_stblock_plan pl;
+        int rc = route_and_plan(b.desc, &r, &pl);
+        if (!rc) rc = append([&](PackList& T) { return pack_fill_block(T, b.desc, r, b.params, pl, b.ws, true); });
+        if (rc) return rc;
+    }
+    if (hd) {
+        if (!hp || !hws) return fail(STGCN_ERR_INVALID, "stgcn_prepack: head params / ws are NULL");
+        stgcn_outblock_plan pl;
+        int rc = stgcn_outblock_plan_query(hd, &pl);
+        if (!rc) rc = append([&](PackList& T) { return pack_fill_head(T, hd, hp, pl, hws, true); });
+        if (rc) return rc;
+    }
+    if (L.nj == 0 && L.pa.ncounters == 0) return STGCN_OK;
+    if (park && L.nj > 0) {   // parked: the next entry point fuses it with the thin first layer or launches it (flush_pending_pack)
+        g_pending_pack.valid = true;
+        g_pending_pack.L = L;
+        g_pending_pack.st = (hipStream_t)stream;
+        return STGCN_OK;
+    }
+    return launch_pack_list("prepack", L, (hipStream_t)stream);
+}
+
+int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
+                           const stgcn_head_loss* hl, const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx,
+                           const stgcn_ln_hook* dx_hook, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    stgcn_outblock_plan pl;
+    int rc = stgcn_outblock_plan_query(d, &pl);
+    if (rc) return rc;
+    if (!P || !x || (!dout && !hl) || !saved || !ws || !G) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: NULL buffer");
+    if (d->need_dx && !dx) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: need_dx set but dx is NULL");
+    rc = check_dx_hook("stgcn_outblock_backward", dx_hook, d->N, d->c_in, d->need_dx, d->dtype);
+    if (rc) return rc;
+    const HeadGeom g = head_geom(d);
+    hipStream_t st = (hipStream_t)stream;
+    g_prof_tag = 0;
+    g_bf16 = d->dtype == STGCN_DTYPE_BF16;
+    float* part = ws + pl.ws_part;
+    const int training = d->training && d->droprate > 0.f;
+    const bool own_rowstats = (fuse_mask() & FUSE_ROWSTATS) && d->c0 == d->c1 && d->c0 == 128;
+
+    // ---- fc2 / dropout / relu / fc1 backward ------------------------------------------------------------------
+    {
+        FcBwdArgs a = zeroed<FcBwdArgs>();
+        a.dout = dout; a.hd = saved + pl.sv_hd; a.w2 = P->fc2_w; a.W1d = ws + pl.ws_W1d; a.dh1 = ws + pl.ws_dh1; a.dyln = ws + pl.ws_dyln;
+        a.part = part + g.off_fc; a.rows = g.rows; a.c0 = d->c0; a.c1 = d->c1; a.KCH = d->c1 / 16;
+        a.grad_scale = training ? 1.0f / (1.0f - d->droprate) : 1.0f;
+        if (hl) {
+            a.pred = hl->pred; a.target = hl->target; a.target_index = reinterpret_cast<const long*>(hl->target_index_dev);
+            a.target_index_stride = (long)hl->target_index_stride; a.loss_scale = hl->grad_scale;
+            a.target_window = reinterpret_cast<const long*>(hl->target_window_dev); a.target_window_elems = (unsigned)(g.rows / d->B);
+        }
+        if (own_rowstats) {   // the head's LayerNorm-backward row partials in this kernel's epilogue (dyln is that LayerNorm's output gradient)
+            a.rs.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b); a.rs.U = saved + pl.sv_U; a.rs.S = saved + pl.sv_S; a.rs.gamma = P->ln_w;
+            a.rs.mean = saved + pl.sv_mean; a.rs.rstd = saved + pl.sv_rstd; a.rs.N = d->N; a.rs.C = d->c0; a.rs.act = d->act; a.rs.training = 0;
+            a.rs.keep_scale = 1.f;
+        }
+        const size_t lds = (size_t)(head_fc_tile_rows() * (d->c1 + 4) + 8 * d->c1 + 16) * sizeof(float);
+        if (head_fc_tile_rows() == 16) {
+            if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+            else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+        } else if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+        else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+    }
+    // ---- fc1 weight gradient (needs dh1 only) ----------------------------------------------------------------------------
+    TconvBwdWeightArgs wa = zeroed<TconvBwdWeightArgs>();
+    wa.ts = make_taps(saved + pl.sv_yln, d->c0, 1, d->N, g.T1, g.T1, 1, g.rows);
+    wa.dZ = ws + pl.ws_dh1; wa.part = part + g.wf.off; wa.NC = d->c1; wa.Mpad = g.wf.Mpad; wa.rows_per_chunk = g.wf.rows_per_chunk;
+    wa.chunks = g.wf.chunks;
+    const TconvBwdWeightArgs wfc = wa;      // (kept: it may share the conv weight gradient's launch at the end of the call)
+    TconvBwdWeightArgs wcv = wa;
+    wcv.ts.src = x; wcv.ts.C = d->c_in; wcv.ts.taps = d->Ko; wcv.ts.Tsrc = d->T; wcv.ts.Tdst = g.T1;
+    wcv.dZ = ws + pl.ws_dZ; wcv.part = part + g.wc.off; wcv.NC = g.NC; wcv.Mpad = g.wc.Mpad; wcv.rows_per_chunk = g.wc.rows_per_chunk;
+    wcv.chunks = g.wc.chunks;
+    const bool pair = wgrad_pair_ok(wcv, g.wc, wfc, g.wf);
+    if (!pair) {
+        rc = launch_bwd_weight("head.fc1_bwd_weight", wfc, g.wf, st);
+        if (rc) return rc;
+    }
+    // ---- LayerNorm + gate backward ---------------------------------------------------------------------------------
+    LnBwdArgs ln = zeroed<LnBwdArgs>();
+    ln.dy = ws + pl.ws_dyln; ln.U = saved + pl.sv_U; ln.S = saved + pl.sv_S; ln.gamma = P->ln_w;
+    ln.mean = saved + pl.sv_mean; ln.rstd = saved + pl.sv_rstd; ln.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b);
+    ln.dZ = ws + pl.ws_dZ; ln.dgam_part = part + g.off_ln_g; ln.dbet_part = part + g.off_ln_b;
+    ln.n = d->N * d->c0; ln.N = d->N; ln.C = d->c0; ln.act = d->act; ln.training = 0; ln.spg = g.ln_spg; ln.slabs = g.slabs;
+    ln.keep_scale = 1.f; ln.thresh = 0;
+    if (!own_rowstats)
+        STGCN_LAUNCH_ET("head.ln_bwd_rowstats", st, (ln_bwd_rowstats_kernel<ET>), dim3(cdiv(g.slabs * (ln.n / 4), kThreads)), dim3(kThreads), 0, ln);
+    if (cdiv(ln.n / 4, kThreads) >= kLnBigColgroups) {
+        ln.slabconst = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b + 2 * g.rows);
+        STGCN_LAUNCH("head.ln_slab_consts", st, ln_slab_consts_kernel, dim3((unsigned)g.slabs), dim3(kThreads), 64, ln);
+    }
+    const bool fused_ln = g.fused_ln_bwd && own_rowstats;   // LayerNorm + gate backward inside the dense transposed conv below
+    if (!fused_ln)
+        STGCN_LAUNCH_ET("head.ln_gate_bwd", st, (ln_gate_bwd_kernel<ET>), dim3(cdiv(ln.n / 4, kThreads), g.ln_sg), dim3(kThreads),
+                        (8 + 2 * g.ln_spg) * sizeof(float), ln);
+    // ---- conv backward-data ---------------------------------------------------------------------------------------------
+    bool hook_pending = false;
+    if (d->need_dx && g.dense_bwd) {
+        Tconv4Args aa = zeroed<Tconv4Args>();
+        aa.f.ts = make_taps(ws + pl.ws_dZ, g.NC, 1, d->N, 1, 1, 1, g.rows);
+        aa.f.Wp = ws + pl.ws_Wd; aa.f.KCH = g.NC / 16; aa.f.Cout = 128;
+        aa.out = dx; aa.outT = d->T; aa.outC = d->c_in;
+        const bool epi = dx_hook && dx_hook->rowstat && dx_hook->C == d->c_in && (d->c_in == 64 || d->c_in == 128) && dx_hook->N == d->N;
+        if (epi) aa.rs = rowstat_out(dx_hook);
+        if (fused_ln) {
+            aa.lnb.dy = ln.dy; aa.lnb.U = ln.U; aa.lnb.S = ln.S; aa.lnb.gamma = ln.gamma; aa.lnb.mean = ln.mean; aa.lnb.rstd = ln.rstd;
+            aa.lnb.rowstat = ln.rowstat; aa.lnb.dZ = ln.dZ; aa.lnb.dgam = ln.dgam_part; aa.lnb.N = d->N; aa.lnb.C = d->c0; aa.lnb.act = d->act;
+            aa.lnb.dbet = g_bf16 ? ln.dbet_part : nullptr;
+        }
+        rc = launch_tconv_fwd4<true>("head.tconv_bwd_data", aa, st);
+        if (rc) return rc;
+        if (dx_hook && dx_hook->rowstat && !epi) hook_pending = true;
+    } else if (d->need_dx) {
+        TconvBwdDataArgs a = zeroed<TconvBwdDataArgs>();
+        a.ts = make_taps(ws + pl.ws_dZ, g.NC, d->Ko, d->N, g.T1, d->T, -1, g.rows_in);
+        a.Wp = ws + pl.ws_Wd; a.KCH = d->Ko * g.NC / 16; a.Cin = d->c_in; a.Gmask = nullptr; a.dX = dx;
+        rc = launch_bwd_data("head.tconv_bwd_data", a, g.CPin / 16, st);
+        if (rc) return rc;
+        if (dx_hook && dx_hook->rowstat) hook_pending = true;
+    }
+    // ---- conv weight gradient (needs dZ, which the fused transposed conv above writes) --------------------------------------------
+    rc = pair ? launch_wgrad_pair("head.wgrad_pair", wcv, g.wc, wfc, g.wf, st) : launch_bwd_weight("head.tconv_bwd_weight", wcv, g.wc, st);
+    if (rc) return rc;
+    if (hook_pending) {   // the kernel that formed dx had no epilogue for it
+        rc = launch_hook_rowstats(dx_hook, dx, (long)d->B * d->T, st);
+        if (rc) return rc;
+    }
+    // ---- final reduction (deferred to stgcn_grad_flush when asked) ------------------------------------------------------------
+    if (d->defer_reduce) return STGCN_OK;
+    ReduceList RL;
+    reduce_jobs_head(RL, d, g, part, ws + pl.ws_dyln, G);
+    return launch_reduce_list("head.reduce", RL, st);
+}
+// the job list of a whole-model flush with the optimizer table attached (stgcn_grad_flush, stgcn_grad_flush_optim); need_v: the kind keeps
+// exp_avg_sq (every kind but Lion)
+int flush_job_list(ReduceList& RL, const char* who, int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                   const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count, bool need_v) {
+    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "%s: bad block table", who);
+    for (int i = 0; i < n_blocks; ++i) {
+        const stgcn_stblock_desc* d = blocks[i].desc;
+        BlockRoute r;
+        stgcn_stblock_plan pl;
+        int rc = route_and_plan(d, &r, &pl);
+        if (rc) return rc;
+        if (!blocks[i].grads || !blocks[i].ws) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in block %d", who, i);
+        reduce_jobs_block(RL, d, r, blocks[i].ws + pl.ws_part, blocks[i].grads);
+    }
+    if (head_desc) {
+        stgcn_outblock_plan pl;
+        int rc = stgcn_outblock_plan_query(head_desc, &pl);
+        if (rc) return rc;
+        if (!head_grads || !head_ws) return fail(STGCN_ERR_INVALID, "%s: NULL head pointer", who);
+        const HeadGeom g = head_geom(head_desc);
+        reduce_jobs_head(RL, head_desc, g, head_ws + pl.ws_part, head_ws + pl.ws_dyln, head_grads);
+    }
+    if (opt_count > 0) {
+        int matched = 0;
+        for (int k = 0; k < RL.nj; ++k)
+            for (int i = 0; i < opt_count; ++i)
+                if (opt[i].grad == RL.ra.job[k].dst) {
+                    if (!opt[i].param || !opt[i].exp_avg || (need_v && !opt[i].exp_avg_sq)) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in optimizer entry %d", who, i);
+                    RL.ra.job[k].p = opt[i].param; RL.ra.job[k].m = opt[i].exp_avg; RL.ra.job[k].v = opt[i].exp_avg_sq;
+                    if (((reinterpret_cast<uintptr_t>(opt[i].param) | reinterpret_cast<uintptr_t>(opt[i].exp_avg) | reinterpret_cast<uintptr_t>(opt[i].exp_avg_sq)) & 15) != 0)
+                        RL.ra.job[k].dvec = 0;   // (the 16-byte form of the state update needs aligned state tensors)
+                    ++matched;
+                    break;
+                }
+        if (matched != opt_count) return fail(STGCN_ERR_INVALID, "%s: %d of %d optimizer entries have no gradient in this flush", who, opt_count - matched, opt_count);
+    }
+    return STGCN_OK;
+}
+
+// NAdamW / Lion constants beyond ReduceArgs / AdamwArgs, formed in double like torch forms them
+OptimExtra optim_extra(const stgcn_optim_hyper* h) {
+    OptimExtra x = zeroed<OptimExtra>();
+    x.omb1 = (float)(1.0 - h->beta1);
+    x.omb2 = (float)(1.0 - h->beta2);
+    x.mu_k = (float)(h->momentum_decay * log(0.96));
+    x.mu_prod = h->mu_product;
+    x.mu_dev = h->kind == STGCN_OPT_NADAMW ? h->mu_product_dev : nullptr;
+    x.mu_job = -1;
+    return x;
+}
+int check_optim_hyper(const stgcn_optim_hyper* h, const char* who) {
+    if (!h) return fail(STGCN_ERR_INVALID, "%s: NULL hyper-parameters", who);
+    if (h->kind != STGCN_OPT_ADAMW && h->kind != STGCN_OPT_NADAMW && h->kind != STGCN_OPT_LION)
+        return fail(STGCN_ERR_INVALID, "%s: unknown optimizer kind %d", who, (int)h->kind);
+    return STGCN_OK;
+}
+}  // namespace
 
 int stgcn_outblock_plan_query(const stgcn_outblock_desc* d, stgcn_outblock_plan* p) {
     int rc = head_check(d);
@@ -143,35 +389,6 @@ int stgcn_outblock_plan_query(const stgcn_outblock_desc* d, stgcn_outblock_plan*
     return STGCN_OK;
 }
 
-} // extern "C" (helper below has C++ linkage)
-namespace {
-bool pack_fill_head(PackList& L, const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const stgcn_outblock_plan& pl, float* ws,
-                    bool all) {
-    const HeadGeom g = head_geom(d);
-    bool ok = true;
-    ok &= L.add(PK_TCONV_FWD, g.NC * g.KP, ws + pl.ws_Wp, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, g.KCH);
-    if (d->need_dx || all) {
-        if (g.dense_bwd)   // same footprint (NC x Ko*c_in floats), K = NC
-            ok &= L.add(PK_TCONV_BWDT, g.NC * d->Ko * d->c_in, ws + pl.ws_Wd, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, g.NC / 16);
-        else
-            ok &= L.add(PK_TCONV_BWD, d->Ko * g.NC * g.CPin, ws + pl.ws_Wd, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko,
-                        d->Ko * g.NC / 16);
-    }
-    ok &= L.add(PK_TCONV_BIAS, g.NC, ws + pl.ws_b, P->tc_w, P->tc_b, P->tc_aw, P->tc_ab, d->c_in, d->c0, d->Ko, 0);
-    ok &= L.add(PK_LIN_FWD, d->c0 * d->c1, ws + pl.ws_W1p, P->fc1_w, nullptr, nullptr, nullptr, d->c0, d->c1, 1, d->c0 / 16);
-    ok &= L.add(PK_LIN_BWD, d->c1 * d->c0, ws + pl.ws_W1d, P->fc1_w, nullptr, nullptr, nullptr, d->c0, d->c1, 1, d->c1 / 16);
-    ok &= L.add(PK_ZERO, (int)pl.chain_words, ws + pl.ws_chain, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0);   // control words of the fused forward
-    return ok;
-}
-}  // namespace
-extern "C" {
-
-} // extern "C"
-namespace {
-int prepack_impl(int32_t n_blocks, const stgcn_prepack_block* blocks, const stgcn_outblock_desc* hd, const stgcn_outblock_params* hp,
-                 float* hws, int32_t n_counters, const stgcn_step_counter* counters, void* stream, bool park);
-}
-extern "C" {
 int stgcn_prepack(int32_t n_blocks, const stgcn_prepack_block* blocks, const stgcn_outblock_desc* hd, const stgcn_outblock_params* hp,
                   float* hws, int32_t n_counters, const stgcn_step_counter* counters, void* stream) {
     return prepack_impl(n_blocks, blocks, hd, hp, hws, n_counters, counters, stream, false);
@@ -183,69 +400,6 @@ int stgcn_prepack_park(int32_t n_blocks, const stgcn_prepack_block* blocks, cons
                        float* hws, int32_t n_counters, const stgcn_step_counter* counters, void* stream) {
     return prepack_impl(n_blocks, blocks, hd, hp, hws, n_counters, counters, stream, true);
 }
-} // extern "C"
-namespace {
-int prepack_impl(int32_t n_blocks, const stgcn_prepack_block* blocks, const stgcn_outblock_desc* hd, const stgcn_outblock_params* hp,
-                 float* hws, int32_t n_counters, const stgcn_step_counter* counters, void* stream, bool park) {
-    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "stgcn_prepack: bad block list");
-    if (n_counters < 0 || n_counters > kMaxStepCounters || (n_counters > 0 && !counters))
-        return fail(STGCN_ERR_INVALID, "stgcn_prepack: at most %d step counters", kMaxStepCounters);
-    STGCN_FLUSH_PENDING_PACK();   // (a pack parked by an earlier call that no forward picked up)
-    // one launch for the whole model while the job table holds it; models with many ST blocks (Kt = 2, n_his = 12 allows 5) spill into
-    // further launches (the step counters ride on the first one)
-    g_prof_tag = 0;
-    PackList L;
-    L.pa.ncounters = n_counters;
-    for (int k = 0; k < n_counters; ++k) {
-        if (!counters[k].ptr) return fail(STGCN_ERR_INVALID, "stgcn_prepack: NULL step counter %d", k);
-        L.pa.cptr[k] = reinterpret_cast<long*>(counters[k].ptr); L.pa.cinc[k] = (long)counters[k].inc; L.pa.cmod[k] = (long)counters[k].mod;
-    }
-    auto flush_list = [&]() -> int {
-        const int rc = launch_pack_list("prepack", L, (hipStream_t)stream);
-        L = PackList();
-        return rc;
-    };
-    for (int i = 0; i < n_blocks; ++i) {
-        const stgcn_prepack_block& b = blocks[i];
-        if (!b.desc || !b.params || !b.ws) return fail(STGCN_ERR_INVALID, "stgcn_prepack: NULL entry in block %d", i);
-        stgcn_stblock_plan pl;
-        int rc = stgcn_stblock_plan_query(b.desc, &pl);
-        if (rc) return rc;
-        PackList trial = L;
-        if (!pack_fill_block(trial, b.desc, b.params, pl, b.ws, true)) {   // does not fit behind the jobs collected so far
-            if (L.nj == 0) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_prepack: one block needs more than %d pack jobs", kMaxPackJobs);
-            rc = flush_list();
-            if (rc) return rc;
-            trial = L;
-            if (!pack_fill_block(trial, b.desc, b.params, pl, b.ws, true)) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_prepack: pack job table overflow");
-        }
-        L = trial;
-    }
-    if (hd) {
-        if (!hp || !hws) return fail(STGCN_ERR_INVALID, "stgcn_prepack: head params / ws are NULL");
-        stgcn_outblock_plan pl;
-        int rc = stgcn_outblock_plan_query(hd, &pl);
-        if (rc) return rc;
-        PackList trial = L;
-        if (!pack_fill_head(trial, hd, hp, pl, hws, true)) {
-            rc = flush_list();
-            if (rc) return rc;
-            trial = L;
-            if (!pack_fill_head(trial, hd, hp, pl, hws, true)) return fail(STGCN_ERR_UNSUPPORTED, "stgcn_prepack: pack job table overflow");
-        }
-        L = trial;
-    }
-    if (L.nj == 0 && L.pa.ncounters == 0) return STGCN_OK;
-    if (park && L.nj > 0) {   // parked: the next entry point fuses it with the thin first layer or launches it (flush_pending_pack)
-        g_pending_pack.valid = true;
-        g_pending_pack.L = L;
-        g_pending_pack.st = (hipStream_t)stream;
-        return STGCN_OK;
-    }
-    return launch_pack_list("prepack", L, (hipStream_t)stream);
-}
-} // namespace
-extern "C" {
 
 int stgcn_outblock_forward(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, float* out, float* saved,
                            float* ws, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream) {
@@ -269,9 +423,8 @@ int stgcn_outblock_forward(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         if (rc) return rc;
     }
 
-    TconvFwdArgs t;
-    memset(&t, 0, sizeof(t));
-    t.ts.src = x; t.ts.C = d->c_in; t.ts.taps = d->Ko; t.ts.N = d->N; t.ts.Tsrc = d->T; t.ts.Tdst = g.T1; t.ts.dir = 1; t.ts.rows = g.rows;
+    TconvFwdArgs t = zeroed<TconvFwdArgs>();
+    t.ts = make_taps(x, d->c_in, d->Ko, d->N, d->T, g.T1, 1, g.rows);
     t.Wp = ws + pl.ws_Wp; t.bias = ws + pl.ws_b; t.KCH = g.KCH; t.Cout = d->c0; t.act = d->act;
     t.U = saved + pl.sv_U; t.S = saved + pl.sv_S; t.rowstat = reinterpret_cast<float2*>(saved + pl.sv_rowstat);
 
@@ -305,11 +458,9 @@ int stgcn_outblock_forward(const stgcn_outblock_desc* d, const stgcn_outblock_pa
             else if (tk4) { tm = 4; ticket = 1; }
         }
         if (tm) {
-            Tconv4Args aa;
-            memset(&aa, 0, sizeof(aa));
+            Tconv4Args aa = zeroed<Tconv4Args>();
             aa.f = t;
-            HeadFcTail f;
-            memset(&f, 0, sizeof(f));
+            HeadFcTail f = zeroed<HeadFcTail>();
             const int TR = 16 * tm, tiles = cdiv(g.rows, TR);
             f.chain.words = reinterpret_cast<unsigned*>(ws + pl.ws_chain); f.chain.ncount = (int)g.slabs; f.chain.total = (unsigned)tiles;
             f.chain.spin = g_chain_spin_ticks;
@@ -329,8 +480,7 @@ int stgcn_outblock_forward(const stgcn_outblock_desc* d, const stgcn_outblock_pa
     rc = launch_tconv_fwd("head.tconv_fwd", t, st);
     if (rc) return rc;
 
-    LnFwdArgs ln;
-    memset(&ln, 0, sizeof(ln));
+    LnFwdArgs ln = zeroed<LnFwdArgs>();
     ln.U = saved + pl.sv_U; ln.S = saved + pl.sv_S; ln.gamma = P->ln_w; ln.beta = P->ln_b; ln.y = saved + pl.sv_yln;
     ln.mean = saved + pl.sv_mean; ln.rstd = saved + pl.sv_rstd; ln.rowstat = reinterpret_cast<const float2*>(saved + pl.sv_rowstat);
     ln.n = d->N * d->c0; ln.N = d->N; ln.C = d->c0; ln.act = d->act; ln.training = 0;
@@ -343,45 +493,29 @@ int stgcn_outblock_forward(const stgcn_outblock_desc* d, const stgcn_outblock_pa
         if (rc) return rc;
     }
 
-    FcFwdArgs f;
-    memset(&f, 0, sizeof(f));
+    FcFwdArgs f = zeroed<FcFwdArgs>();
     if (fuse_ln) f.ln = ln;
-    f.ts.src = saved + pl.sv_yln; f.ts.C = d->c0; f.ts.taps = 1; f.ts.N = d->N; f.ts.Tsrc = g.T1; f.ts.Tdst = g.T1; f.ts.dir = 1;
-    f.ts.rows = g.rows;
+    f.ts = make_taps(saved + pl.sv_yln, d->c0, 1, d->N, g.T1, g.T1, 1, g.rows);
     f.W1p = ws + pl.ws_W1p; f.b1 = P->fc1_b; f.w2 = P->fc2_w; f.b2 = P->fc2_b; f.hd = saved + pl.sv_hd; f.out = out;
     f.KCH = d->c0 / 16; f.c1 = d->c1; f.training = d->training && d->droprate > 0.f;
     f.keep_scale = 1.0f / (1.0f - d->droprate); f.thresh = drop_thresh(d->droprate); f.seed = seed; f.offset = offset;
     f.offset_dev = offset_dev;
     // (big heads: 32-row tiles halve the fc1 weight bytes a row streams -- C5 fc_fwd 72 -> 59 us, pass r4-31; the backward kernel loses with them)
-    const int fct = (getenv("STGCN_HEAD_FC_TILE") || g.rows <= 32768) ? head_fc_tile_rows() : 32;
+    const int fct = (head_fc_tile_knob() || g.rows <= 32768) ? head_fc_tile_rows() : 32;
     const size_t lds = (size_t)(kTileHdr + fct * (128 + 4)) * sizeof(float);
     if (fct == 16) STGCN_LAUNCH_ET("head.fc_fwd", st, (fc_fwd_kernel<1, ET>), dim3(cdiv(g.rows, 16)), dim3(kThreads), lds, f);
     else STGCN_LAUNCH_ET("head.fc_fwd", st, (fc_fwd_kernel<2, ET>), dim3(cdiv(g.rows, 32)), dim3(kThreads), lds, f);
     return STGCN_OK;
 }
 
-
 int stgcn_outblock_chain_status(const stgcn_outblock_desc* d, const float* ws, uint32_t* sticky, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     stgcn_outblock_plan pl;
-    int rc = stgcn_outblock_plan_query(d, &pl);
+    const int rc = stgcn_outblock_plan_query(d, &pl);
     if (rc) return rc;
-    if (!ws || !sticky) return fail(STGCN_ERR_INVALID, "stgcn_outblock_chain_status: NULL argument");
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail(STGCN_ERR_LAUNCH, "stgcn_outblock_chain_status: stream synchronisation failed");
-    unsigned w = 0;
-    if (hipMemcpy(&w, reinterpret_cast<const unsigned*>(ws + pl.ws_chain) + 2, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(STGCN_ERR_LAUNCH, "stgcn_outblock_chain_status: copy failed");
-    *sticky = w;
-    return STGCN_OK;
+    return read_chain_sticky("stgcn_outblock_chain_status", ws, pl.ws_chain, sticky, stream);
 }
 
-} // extern "C" (the shared implementation has C++ linkage)
-namespace {
-int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
-                           const stgcn_head_loss* hl, const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx,
-                           const stgcn_ln_hook* dx_hook, void* stream);
-}
-extern "C" {
 int stgcn_outblock_backward(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
                             const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx, void* stream) {
     return outblock_backward_impl(d, P, x, dout, nullptr, saved, ws, G, dx, nullptr, stream);
@@ -402,199 +536,6 @@ int stgcn_outblock_backward_loss(const stgcn_outblock_desc* d, const stgcn_outbl
         return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: target_window_dev (window table) needs target_index_dev != NULL");
     return outblock_backward_impl(d, P, x, nullptr, hl, saved, ws, G, dx, dx_hook, stream);
 }
-} // extern "C"
-namespace {
-int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
-                           const stgcn_head_loss* hl, const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx,
-                           const stgcn_ln_hook* dx_hook, void* stream) {
-    STGCN_FLUSH_PENDING_PACK();
-    stgcn_outblock_plan pl;
-    int rc = stgcn_outblock_plan_query(d, &pl);
-    if (rc) return rc;
-    if (!P || !x || (!dout && !hl) || !saved || !ws || !G) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: NULL buffer");
-    if (d->need_dx && !dx) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: need_dx set but dx is NULL");
-    if (dx_hook && dx_hook->rowstat && (dx_hook->N != d->N || dx_hook->C != d->c_in || !d->need_dx))
-        return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: dx_hook describes a LayerNorm over [%d, %d], the input gradient is [%d, %d] per slab",
-                    dx_hook->N, dx_hook->C, d->N, d->c_in);
-    const HeadGeom g = head_geom(d);
-    hipStream_t st = (hipStream_t)stream;
-    g_prof_tag = 0;
-    g_bf16 = d->dtype == STGCN_DTYPE_BF16;
-    if (dx_hook && dx_hook->rowstat && dx_hook->dtype != d->dtype)
-        return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward: dx_hook describes tensors of another dtype than this call");
-    float* part = ws + pl.ws_part;
-    const int training = d->training && d->droprate > 0.f;
-    const bool own_rowstats = (fuse_mask() & FUSE_ROWSTATS) && d->c0 == d->c1 && d->c0 == 128;
-
-    // ---- fc2 / dropout / relu / fc1 backward ------------------------------------------------------------------
-    {
-        FcBwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.dout = dout; a.hd = saved + pl.sv_hd; a.w2 = P->fc2_w; a.W1d = ws + pl.ws_W1d; a.dh1 = ws + pl.ws_dh1; a.dyln = ws + pl.ws_dyln;
-        a.part = part + g.off_fc; a.rows = g.rows; a.c0 = d->c0; a.c1 = d->c1; a.KCH = d->c1 / 16;
-        a.grad_scale = training ? 1.0f / (1.0f - d->droprate) : 1.0f;
-        if (hl) {
-            a.pred = hl->pred; a.target = hl->target; a.target_index = reinterpret_cast<const long*>(hl->target_index_dev);
-            a.target_index_stride = (long)hl->target_index_stride; a.loss_scale = hl->grad_scale;
-            a.target_window = reinterpret_cast<const long*>(hl->target_window_dev); a.target_window_elems = (unsigned)(g.rows / d->B);
-        }
-        if (own_rowstats) {   // the head's LayerNorm-backward row partials in this kernel's epilogue (dyln is that LayerNorm's output gradient)
-            a.rs.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b); a.rs.U = saved + pl.sv_U; a.rs.S = saved + pl.sv_S; a.rs.gamma = P->ln_w;
-            a.rs.mean = saved + pl.sv_mean; a.rs.rstd = saved + pl.sv_rstd; a.rs.N = d->N; a.rs.C = d->c0; a.rs.act = d->act; a.rs.training = 0;
-            a.rs.keep_scale = 1.f;
-        }
-        const size_t lds = (size_t)(head_fc_tile_rows() * (d->c1 + 4) + 8 * d->c1 + 16) * sizeof(float);
-        if (head_fc_tile_rows() == 16) {
-            if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
-            else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
-        } else if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
-        else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
-    }
-    // ---- fc1 weight gradient (needs dh1 only) ----------------------------------------------------------------------------
-    TconvBwdWeightArgs wa;
-    memset(&wa, 0, sizeof(wa));
-    wa.ts.src = saved + pl.sv_yln; wa.ts.C = d->c0; wa.ts.taps = 1; wa.ts.N = d->N; wa.ts.Tsrc = g.T1; wa.ts.Tdst = g.T1; wa.ts.dir = 1;
-    wa.ts.rows = g.rows;
-    wa.dZ = ws + pl.ws_dh1; wa.part = part + g.wf.off; wa.NC = d->c1; wa.Mpad = g.wf.Mpad; wa.rows_per_chunk = g.wf.rows_per_chunk;
-    wa.chunks = g.wf.chunks;
-    const TconvBwdWeightArgs wfc = wa;      // (kept: it may share the conv weight gradient's launch at the end of the call)
-    TconvBwdWeightArgs wcv = wa;
-    wcv.ts.src = x; wcv.ts.C = d->c_in; wcv.ts.taps = d->Ko; wcv.ts.Tsrc = d->T; wcv.ts.Tdst = g.T1;
-    wcv.dZ = ws + pl.ws_dZ; wcv.part = part + g.wc.off; wcv.NC = g.NC; wcv.Mpad = g.wc.Mpad; wcv.rows_per_chunk = g.wc.rows_per_chunk;
-    wcv.chunks = g.wc.chunks;
-    const bool pair = wgrad_pair_ok(wcv, g.wc, wfc, g.wf);
-    if (!pair) {
-        rc = launch_bwd_weight("head.fc1_bwd_weight", wfc, g.wf, st);
-        if (rc) return rc;
-    }
-    // ---- LayerNorm + gate backward ---------------------------------------------------------------------------------
-    LnBwdArgs ln;
-    memset(&ln, 0, sizeof(ln));
-    ln.dy = ws + pl.ws_dyln; ln.U = saved + pl.sv_U; ln.S = saved + pl.sv_S; ln.gamma = P->ln_w;
-    ln.mean = saved + pl.sv_mean; ln.rstd = saved + pl.sv_rstd; ln.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b);
-    ln.dZ = ws + pl.ws_dZ; ln.dgam_part = part + g.off_ln_g; ln.dbet_part = part + g.off_ln_b;
-    ln.n = d->N * d->c0; ln.N = d->N; ln.C = d->c0; ln.act = d->act; ln.training = 0; ln.spg = g.ln_spg; ln.slabs = g.slabs;
-    ln.keep_scale = 1.f; ln.thresh = 0;
-    if (!own_rowstats)
-        STGCN_LAUNCH_ET("head.ln_bwd_rowstats", st, (ln_bwd_rowstats_kernel<ET>), dim3(cdiv(g.slabs * (ln.n / 4), kThreads)), dim3(kThreads), 0, ln);
-    if (cdiv(ln.n / 4, kThreads) >= kLnBigColgroups) {
-        ln.slabconst = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b + 2 * g.rows);
-        STGCN_LAUNCH("head.ln_slab_consts", st, ln_slab_consts_kernel, dim3((unsigned)g.slabs), dim3(kThreads), 64, ln);
-    }
-    const bool fused_ln = g.fused_ln_bwd && own_rowstats;   // LayerNorm + gate backward inside the dense transposed conv below
-    if (!fused_ln)
-        STGCN_LAUNCH_ET("head.ln_gate_bwd", st, (ln_gate_bwd_kernel<ET>), dim3(cdiv(ln.n / 4, kThreads), g.ln_sg), dim3(kThreads),
-                        (8 + 2 * g.ln_spg) * sizeof(float), ln);
-    // ---- conv backward-data ---------------------------------------------------------------------------------------------
-    bool hook_pending = false;
-    if (d->need_dx && g.dense_bwd) {
-        Tconv4Args aa;
-        memset(&aa, 0, sizeof(aa));
-        aa.f.ts.src = ws + pl.ws_dZ; aa.f.ts.C = g.NC; aa.f.ts.taps = 1; aa.f.ts.N = d->N; aa.f.ts.Tsrc = 1; aa.f.ts.Tdst = 1; aa.f.ts.dir = 1;
-        aa.f.ts.rows = g.rows;
-        aa.f.Wp = ws + pl.ws_Wd; aa.f.KCH = g.NC / 16; aa.f.Cout = 128;
-        aa.out = dx; aa.outT = d->T; aa.outC = d->c_in;
-        const bool epi = dx_hook && dx_hook->rowstat && dx_hook->C == d->c_in && (d->c_in == 64 || d->c_in == 128) && dx_hook->N == d->N;
-        if (epi) aa.rs = rowstat_out(dx_hook);
-        if (fused_ln) {
-            aa.lnb.dy = ln.dy; aa.lnb.U = ln.U; aa.lnb.S = ln.S; aa.lnb.gamma = ln.gamma; aa.lnb.mean = ln.mean; aa.lnb.rstd = ln.rstd;
-            aa.lnb.rowstat = ln.rowstat; aa.lnb.dZ = ln.dZ; aa.lnb.dgam = ln.dgam_part; aa.lnb.N = d->N; aa.lnb.C = d->c0; aa.lnb.act = d->act;
-            aa.lnb.dbet = g_bf16 ? ln.dbet_part : nullptr;
-        }
-        rc = launch_tconv_fwd4<true>("head.tconv_bwd_data", aa, st);
-        if (rc) return rc;
-        if (dx_hook && dx_hook->rowstat && !epi) hook_pending = true;
-    } else if (d->need_dx) {
-        TconvBwdDataArgs a;
-        memset(&a, 0, sizeof(a));
-        a.ts.src = ws + pl.ws_dZ; a.ts.C = g.NC; a.ts.taps = d->Ko; a.ts.N = d->N; a.ts.Tsrc = g.T1; a.ts.Tdst = d->T; a.ts.dir = -1;
-        a.ts.rows = g.rows_in;
-        a.Wp = ws + pl.ws_Wd; a.KCH = d->Ko * g.NC / 16; a.Cin = d->c_in; a.Gmask = nullptr; a.dX = dx;
-        rc = launch_bwd_data("head.tconv_bwd_data", a, g.CPin / 16, st);
-        if (rc) return rc;
-        if (dx_hook && dx_hook->rowstat) hook_pending = true;
-    }
-    // ---- conv weight gradient (needs dZ, which the fused transposed conv above writes) --------------------------------------------
-    rc = pair ? launch_wgrad_pair("head.wgrad_pair", wcv, g.wc, wfc, g.wf, st) : launch_bwd_weight("head.tconv_bwd_weight", wcv, g.wc, st);
-    if (rc) return rc;
-    if (hook_pending) {   // the kernel that formed dx had no epilogue for it: the hooked LayerNorm's row partials from a pass over dx
-        LnBwdArgs hl;
-        memset(&hl, 0, sizeof(hl));
-        const LnRowstatOut o = rowstat_out(dx_hook);
-        hl.dy = dx; hl.y = o.y; hl.beta = o.beta; hl.gamma = o.gamma; hl.rowstat = o.rowstat;
-        hl.n = o.N * o.C; hl.N = o.N; hl.C = o.C; hl.act = o.act; hl.training = o.training; hl.slabs = (long)d->B * d->T;
-        hl.keep_scale = o.keep_scale; hl.thresh = o.thresh; hl.seed = o.seed; hl.offset = o.offset; hl.offset_dev = o.offset_dev;
-        STGCN_LAUNCH_ET("ln_bwd_rowstats", st, (ln_bwd_rowstats_kernel<ET>), dim3(cdiv(hl.slabs * (hl.n / 4), kThreads)), dim3(kThreads), 0, hl);
-    }
-    // ---- final reduction (deferred to stgcn_grad_flush when asked) ------------------------------------------------------------
-    if (d->defer_reduce) return STGCN_OK;
-    ReduceList RL;
-    reduce_jobs_head(RL, d, g, part, ws + pl.ws_dyln, G);
-    return launch_reduce_list("head.reduce", RL, st);
-}
-// the job list of a whole-model flush with the optimizer table attached (stgcn_grad_flush, stgcn_grad_flush_optim); need_v: the kind keeps
-// exp_avg_sq (every kind but Lion)
-int flush_job_list(ReduceList& RL, const char* who, int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
-                   const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count, bool need_v) {
-    if (n_blocks < 0 || (n_blocks > 0 && !blocks)) return fail(STGCN_ERR_INVALID, "%s: bad block table", who);
-    for (int i = 0; i < n_blocks; ++i) {
-        const stgcn_stblock_desc* d = blocks[i].desc;
-        stgcn_stblock_plan pl;
-        int rc = stgcn_stblock_plan_query(d, &pl);
-        if (rc) return rc;
-        if (!blocks[i].grads || !blocks[i].ws) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in block %d", who, i);
-        const Derived v = derive(d);
-        const BwdGeom bg = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, v.terms, d->need_dx);
-        reduce_jobs_block(RL, d, v, bg, blocks[i].ws + pl.ws_part, blocks[i].grads);
-    }
-    if (head_desc) {
-        stgcn_outblock_plan pl;
-        int rc = stgcn_outblock_plan_query(head_desc, &pl);
-        if (rc) return rc;
-        if (!head_grads || !head_ws) return fail(STGCN_ERR_INVALID, "%s: NULL head pointer", who);
-        const HeadGeom g = head_geom(head_desc);
-        reduce_jobs_head(RL, head_desc, g, head_ws + pl.ws_part, head_ws + pl.ws_dyln, head_grads);
-    }
-    if (opt_count > 0) {
-        int matched = 0;
-        for (int k = 0; k < RL.nj; ++k)
-            for (int i = 0; i < opt_count; ++i)
-                if (opt[i].grad == RL.ra.job[k].dst) {
-                    if (!opt[i].param || !opt[i].exp_avg || (need_v && !opt[i].exp_avg_sq)) return fail(STGCN_ERR_INVALID, "%s: NULL pointer in optimizer entry %d", who, i);
-                    RL.ra.job[k].p = opt[i].param; RL.ra.job[k].m = opt[i].exp_avg; RL.ra.job[k].v = opt[i].exp_avg_sq;
-                    if (((reinterpret_cast<uintptr_t>(opt[i].param) | reinterpret_cast<uintptr_t>(opt[i].exp_avg) | reinterpret_cast<uintptr_t>(opt[i].exp_avg_sq)) & 15) != 0)
-                        RL.ra.job[k].dvec = 0;   // (the 16-byte form of the state update needs aligned state tensors)
-                    ++matched;
-                    break;
-                }
-        if (matched != opt_count) return fail(STGCN_ERR_INVALID, "%s: %d of %d optimizer entries have no gradient in this flush", who, opt_count - matched, opt_count);
-    }
-    return STGCN_OK;
-}
-
-// NAdamW / Lion constants beyond ReduceArgs / AdamwArgs, formed in double like torch forms them
-OptimExtra optim_extra(const stgcn_optim_hyper* h) {
-    OptimExtra x;
-    memset(&x, 0, sizeof(x));
-    x.omb1 = (float)(1.0 - h->beta1);
-    x.omb2 = (float)(1.0 - h->beta2);
-    x.mu_k = (float)(h->momentum_decay * log(0.96));
-    x.mu_prod = h->mu_product;
-    x.mu_dev = h->kind == STGCN_OPT_NADAMW ? h->mu_product_dev : nullptr;
-    x.mu_job = -1;
-    return x;
-}
-int check_optim_hyper(const stgcn_optim_hyper* h, const char* who) {
-    if (!h) return fail(STGCN_ERR_INVALID, "%s: NULL hyper-parameters", who);
-    if (h->kind != STGCN_OPT_ADAMW && h->kind != STGCN_OPT_NADAMW && h->kind != STGCN_OPT_LION)
-        return fail(STGCN_ERR_INVALID, "%s: unknown optimizer kind %d", who, (int)h->kind);
-    return STGCN_OK;
-}
-
-}  // namespace
-extern "C" {
-
-
 
 int stgcn_adamw_step(const stgcn_adamw_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev, void* stream) {
@@ -602,8 +543,7 @@ int stgcn_adamw_step(const stgcn_adamw_tensor* tensors, int32_t count, float lr,
     if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "stgcn_adamw_step: bad tensor table");
     hipStream_t st = (hipStream_t)stream;
     for (int off = 0; off < count; off += kAdamwMaxTensors) {
-        AdamwArgs a;
-        memset(&a, 0, sizeof(a));
+        AdamwArgs a = zeroed<AdamwArgs>();
         const int n = count - off < kAdamwMaxTensors ? count - off : kAdamwMaxTensors;
         for (int i = 0; i < n; ++i) {
             const stgcn_adamw_tensor& t = tensors[off + i];
@@ -648,8 +588,7 @@ int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stg
     const bool lion = hyper->kind == STGCN_OPT_LION;
     hipStream_t st = (hipStream_t)stream;
     for (int off = 0; off < count; off += kAdamwMaxTensors) {
-        AdamwArgs a;
-        memset(&a, 0, sizeof(a));
+        AdamwArgs a = zeroed<AdamwArgs>();
         const int n = count - off < kAdamwMaxTensors ? count - off : kAdamwMaxTensors;
         for (int i = 0; i < n; ++i) {
             const stgcn_adamw_tensor& t = tensors[off + i];
@@ -682,8 +621,7 @@ int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, co
     int rc = check_optim_hyper(hyper, "stgcn_grad_flush_optim");
     if (rc) return rc;
     if (hyper->kind == STGCN_OPT_ADAMW) {
-        stgcn_adamw_hyper h;
-        memset(&h, 0, sizeof(h));
+        stgcn_adamw_hyper h = zeroed<stgcn_adamw_hyper>();
         h.lr = (float)hyper->lr; h.beta1 = (float)hyper->beta1; h.beta2 = (float)hyper->beta2; h.eps = (float)hyper->eps;
         h.weight_decay = (float)hyper->weight_decay; h.step = hyper->step; h.step_dev = hyper->step_dev; h.lr_dev = hyper->lr_dev;
         return stgcn_grad_flush(n_blocks, blocks, head_desc, head_grads, head_ws, opt, opt_count, &h, stream);
@@ -735,13 +673,6 @@ int stgcn_mse_loss_grad_windows(const float* pred, const float* target, int64_t 
     return STGCN_OK;
 }
 
-// element count of a batch from which stgcn_eval_accumulate takes the partial-slab form (STGCN_EVAL_BIG, read per call: the tests force
-// either form on one shape -- 0 forces the slabs, a huge value the single workgroup)
-static long eval_big_threshold() {
-    const char* e = getenv("STGCN_EVAL_BIG");
-    return e ? atol(e) : 32768;
-}
-
 int stgcn_eval_arm(double* state, int64_t* pos, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     if (!state) return fail(STGCN_ERR_INVALID, "stgcn_eval_arm: state is NULL");
@@ -782,13 +713,13 @@ int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int
 
 #ifdef STGCN_PHASE_TIMING
 // diagnostic build only: select which kernel stamps its phases, read the stamps back (host buffer of 4096*16 int64)
-int stgcn_debug_phase_select(int kid) {
+extern "C" int stgcn_debug_phase_select(int kid) {   // (diagnostic entries: not in include/stgcn_hip.h)
     hipMemcpyToSymbol(HIP_SYMBOL(stgcn_phase_kid), &kid, sizeof(int));
     static long long zeros[4096 * 16];
     hipMemcpyToSymbol(HIP_SYMBOL(stgcn_phase_buf), zeros, sizeof(zeros));
     return STGCN_OK;
 }
-int stgcn_debug_phase_read(long long* out) {
+extern "C" int stgcn_debug_phase_read(long long* out) {
     hipDeviceSynchronize();
     hipMemcpyFromSymbol(out, HIP_SYMBOL(stgcn_phase_buf), sizeof(long long) * 4096 * 16);
     return STGCN_OK;

@@ -17,231 +17,6 @@
 
 namespace stgcn {
 
-// ---- which fused kernels replace the stage-per-launch path (host side; plan, launchers and the gradient flush must agree) ----
-// STGCN_FUSE=<bit mask> (read once): 1 = tc2_bwd_kernel (LayerNorm/dropout/gate backward + tmp_conv2 weight gradient + transposed conv in
-// one launch).  Default: everything on; 0 reproduces the round-1 launch sequence (A/B runs, stage tests).
-//                                  2 = tc2_ln_fwd_kernel (tmp_conv2 + gate + LayerNorm + dropout of one slab per workgroup).
-//                                  4 = LayerNorm-backward row partials in the epilogue of the kernel that produces dy (stgcn_ln_hook).
-//                                  8 = tc1_bwd_kernel (Align + gate backward + tmp_conv1 weight gradient + transposed conv in one launch).
-//                                 16 = tc1_fwd_kernel (time-stepping tmp_conv1 + gate + Align forward, weights stationary).
-enum FuseBit { FUSE_TC2_BWD = 1, FUSE_TC2_LN_FWD = 2, FUSE_ROWSTATS = 4, FUSE_TC1_BWD = 8, FUSE_TC1_FWD = 16, FUSE_HEAD_LN_FWD = 32, FUSE_HEAD_LN_BWD = 64 };
-inline int fuse_mask() {
-    static const int m = getenv("STGCN_FUSE") ? atoi(getenv("STGCN_FUSE")) : 0x7fffffff;
-    return m;
-}
-// stage tests: also write the on-chip intermediates of the fused kernels (dZ2) to their round-1 workspace slots
-inline int g_debug_stages = 0;
-inline bool tc2_ln_fwd_fused_ok(int c1, int c2, int Kt, int N) {
-    return (fuse_mask() & FUSE_TC2_LN_FWD) && c1 == 16 && c2 == 64 && Kt >= 2 && Kt <= 4 && N <= 448 && tc2_ln_fwd_lds_bytes(Kt, N) <= 150 * 1024;
-}
-// shapes tc1_bwd_kernel covers (whether a call uses it also depends on need_dx: the kernel always forms the input gradient)
-// test knob (stgcn_set_tc1_bwd_wgs): pretend the device has this many CUs (0 = ask the runtime).  The launch heuristics that size a
-// grid by the CU count -- the (item, step) ranges of the two tc1 kernels, the wave count of tc2_ln_fwd -- then take their small-device
-// branches on the emulator too: ranges cut inside items, the 8-wave variant of tc2_ln_fwd
-inline int g_tc1_bwd_wgs = 0;
-inline int device_cus() {
-    static int cus = 0;
-    if (g_tc1_bwd_wgs > 0) return g_tc1_bwd_wgs;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return cus;
-}
-// workgroups per slab of tc2_ln_fwd_kernel (round 6): 1 when the slabs alone fill the device; 2 / 4 when PP * slabs workgroups still fit the
-// compute units one each (the peers exchange their LayerNorm statistics through L2).  stgcn_set_tc2ln_peers forces 1 / 2 / 4 (0 = this rule).
-constexpr int kTc2LnMaxPeers = 4;
-inline int g_tc2ln_peers = 0;
-inline int tc2_ln_peers(int N, long slabs2) {
-    const int tiles = (N + 15) / 16;
-    int pp = 1;
-    if (g_tc2ln_peers > 0) pp = g_tc2ln_peers;
-    else if (4 * slabs2 <= device_cus()) pp = 4;
-    else if (2 * slabs2 <= device_cus()) pp = 2;
-    if (N > 384) pp = 1;                       // (the peer instances hold at most 24 node tiles per slab)
-    while (pp > 1 && tiles < 2 * pp) pp >>= 1;   // at least two node tiles per workgroup
-    return pp;
-}
-// tc2_bwd_kernel recomputes the gate inputs of tmp_conv2 (and the forward does not store them) for bf16 activations, reads the stored
-// ones for fp32 (see the kernel's header comment for the measurement)
-inline bool tc2_recompute(int dtype_bf16) { return dtype_bf16 != 0; }
-// fewest output steps a range of the two tc1 time-stepping kernels is cut down to when a batch offers fewer (window, node tile) items than
-// the device has compute units (measured at C2 shapes, profiles/r6-08_tc1_small_batch_ranges.txt: bs 4 tc1_bwd 36.0 -> 21.6 us, tc1_fwd
-// 17.6 -> 11.2 us with 2; 1 and 3 are slower -- more partial blocks for the reduction / longer chains)
-inline int tc1_min_steps() { return 2; }
-inline bool tc1_ts_shape(int c_in, int c0, int c1, int Kt) { return c0 == 64 && c1 == 16 && Kt == 3 && (c_in == 16 || c_in == 32 || c_in == 64); }
-inline bool tc1_bwd_shape_ok(int c_in, int c0, int c1, int Kt) {
-    return (fuse_mask() & FUSE_TC1_BWD) && tc1_ts_shape(c_in, c0, c1, Kt) && tc1_bwd_lds_bytes(c0, c_in, Kt) <= 150 * 1024;
-}
-inline bool tc1_fwd_shape_ok(int c_in, int c0, int c1, int Kt) { return (fuse_mask() & FUSE_TC1_FWD) && tc1_ts_shape(c_in, c0, c1, Kt); }
-inline bool tc2_bwd_fused_ok(int c1, int c2, int Kt, int T1, int T2) {
-    return (fuse_mask() & FUSE_TC2_BWD) && c1 == 16 && ((c2 == 64 && Kt >= 2 && Kt <= 4) || (c2 == 128 && Kt == 3)) && T1 <= kTsMaxT &&
-           tc2_bwd_lds_bytes(c2, Kt, T1, T2) <= 80 * 1024;
-}
-
-// ---- which graph-conv implementation a block uses (host side; plan, launchers and stgcn_gso_prepare must agree) -------
-// Slab-resident kernels (gconv_fwd_kernel / gconv_bwd_kernel): up to 512 nodes and as many terms as the backward's LDS
-// footprint allows; everything else runs the tiled GEMM path of stgcn_kernels_gctile.hip.h.  The node threshold is a
-// runtime knob (stgcn_set_gc_tiled_min_nodes) so that both paths can be compared on the same graph.
-inline int g_gc_tiled_min_n = 513;
-// arithmetic of the operator products on the tiled path: 0 = fp32 MFMA (exact fp32, default), 1 = bf16x3 (split operands,
-// fp32-class), 2 = bf16 (stgcn_set_gc_precision; see stgcn_kernels_gctile.hip.h)
-inline int g_gc_precision = 0;
-// operator products of the slab-resident graph conv (N <= 512): 0 exact fp32 MFMAs, 1 bf16x3 (stgcn_kernels_gcslab16.hip.h)
-inline int g_slab_gc_precision = 0;
-// matrix products of the BACKWARD kernels of fp32 blocks: 0 exact fp32 MFMAs (default), 1 "bf16x3" (Mma<f32x>: split operands, three bf16
-// MFMAs per product, ~2^-16 relative -- inside the 1e-3 gradient bar, outside "exact fp32"; stgcn_set_bwd_precision)
-inline int g_bwd_precision = 0;
-inline long gc_operand_cols(long slabs) { return (slabs * 16 + 127) / 128 * 128; }   // CP: rows of the bf16 operand form
-// rows ALLOCATED per operand plane: the wide column tiles of gso_gemm_bf16_big_kernel (up to 320 columns) may run past CP
-inline long gc_operand_alloc(long slabs) { return gc_operand_cols(slabs) + 384; }
-// Leading dimension (bf16 elements) of every 16-bit plane (operator hi / lo, operand form).  NP itself is a power-of-two
-// multiple of 128 for the sizes that matter (8192 nodes: 16 KiB rows), so the 128 rows of a tile would all start in the same
-// L2 channel; the pad (stgcn_set_gc_ld_pad, multiple of 8 elements) staggers them.
-inline int g_gc_ld_pad = 0;
-inline int gc_plane_ld(int NP) { return NP + g_gc_ld_pad; }
-inline bool gc_is_tiled(int N, int terms) {
-    if (N >= g_gc_tiled_min_n) return true;
-    const long NP = (N + 15) / 16 * 16;
-    return ((long)terms * 16 * (NP + 4) + NP * 20) * (long)sizeof(float) > 160 * 1024;
-}
-inline int gc_padded_nodes(int N, int terms) { return gc_is_tiled(N, terms) ? (N + kGtBM - 1) / kGtBM * kGtBM : (N + 15) / 16 * 16; }
-
-// ================================================================================================
-// Geometry of the backward launches and of the partial-sum arena (host + plan use the same numbers)
-// ================================================================================================
-struct WgradGeom {
-    int M, Mtiles, MTW, mchunks, Mpad, NC, rows_per_chunk, chunks;
-    long off;   // arena offset: [chunks][Mpad*NC] then [chunks][NC] bias partials
-    long floats;
-};
-// LayerNorm backward on big slabs (N * C / 4 >= 64 * 256 float4 columns, e.g. the 8192-node graph): every workgroup of
-// ln_gate_bwd_kernel would rebuild the slab constants c1, c2 from N row partials (colgroups x slabs x N x 8 B: 4 GB at
-// C5), so a tiny kernel forms them once per slab (ln_slab_consts_kernel) and the workgroups read two floats per slab.
-constexpr int kLnBigColgroups = 64;
-struct BwdGeom {
-    int ln_spg, ln_sg;       // slabs per group / groups for the LayerNorm parameter partials
-    int al_wgs;              // workgroups of align_gate_bwd (grid-stride over 64-row tiles)
-    WgradGeom w1, w2;
-    long off_ln_g, off_ln_b, off_gc, off_al, total;
-    int gc_stride;           // floats per slab in the graph-conv partials: (terms + 1) * 256
-    int gc_count;            // partial blocks of the graph conv: slabs (slab kernels) or workgroups of the tiled row pass
-    int gc_tiles_per_wg;     // tiled row pass: 16-row tiles per workgroup
-    int al_stride;           // floats per workgroup in the align partials: c0*c1 + c1 (+ 16*2*c0 + 2*c0 on the thin path)
-    int thin;                // first layer handled by the thin kernels (Kt*c_in <= 4, c0 == 64, c1 == 16)
-    int k1;                  // tmp_conv2 / LayerNorm backward fused into tc2_bwd_kernel (no dZ2, no w2 partials; ln_sg = B)
-    int node_tiles;          // ceil(N / 16)
-    int k1_wgs, k1_stride;   // workgroups (min(B * node_tiles, 2 per CU)) and floats per workgroup (Kt*16*NC2 + NC2) of its dW_eff2 | db_eff2 partials
-    long off_k1;
-    int k3;                  // tmp_conv1 / Align backward fused into tc1_bwd_kernel (needs need_dx): no dZ1, no w1 / align partials
-    int k3_wb, k3_wgs, k3_stride;   // windows per workgroup, workgroups (node_tiles * ceil(B / wb)), floats per workgroup
-    long off_k3;
-};
-
-inline WgradGeom wgrad_geom(long rows, int K, int NC, long off, int target_wgs = 256) {
-    WgradGeom g;
-    g.M = K;
-    g.Mtiles = (K + 15) / 16;
-    g.MTW = g.Mtiles <= 3 ? g.Mtiles : 4;   // m-tiles per workgroup (1, 2, 3 or 4)
-    g.mchunks = (g.Mtiles + g.MTW - 1) / g.MTW;
-    g.Mpad = g.mchunks * g.MTW * 16;
-    g.NC = NC;
-    // aim at ~target_wgs workgroups in total (256: one per CU; fewer partials to write and re-read), >= 64 rows per chunk
-    long target = target_wgs / g.mchunks;
-    if (target < 1) target = 1;
-    long rpc = (rows + target - 1) / target;
-    rpc = (rpc + 63) / 64 * 64;   // whole 64-row reduction steps
-    if (rpc < 64) rpc = 64;
-    g.rows_per_chunk = (int)rpc;
-    g.chunks = (int)((rows + rpc - 1) / rpc);
-    g.off = off;
-    g.floats = (long)g.chunks * ((long)g.Mpad * NC + NC);
-    return g;
-}
-
-// The thin first layer (K = Kt * c_in <= 4) as wave-per-tile kernels (round 5, stgcn_kernels_thin.hip.h); STGCN_THIN=0 selects the row-tile
-// kernels of rounds 1 - 4 (A/B runs; the stage tests run both).  Read per call: the tests switch it.
-inline bool thin_wave_tiles() {
-    const char* e = getenv("STGCN_THIN");
-    return !(e && e[0] == '0');
-}
-inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, int Kt, int terms, int need_dx) {
-    BwdGeom g;
-    const int T1 = T - Kt + 1, T2 = T1 - Kt + 1;
-    const long rows1 = (long)B * T1 * N, rows2 = (long)B * T2 * N, slabs1 = (long)B * T1, slabs2 = (long)B * T2;
-    const long n = (long)N * c2, n4 = n / 4;
-    const int colgroups = (int)((n4 + kThreads - 1) / kThreads);
-    int sg = (512 + colgroups - 1) / colgroups;   // ~512 workgroups
-    if (colgroups >= kLnBigColgroups) sg = (4096 + colgroups - 1) / colgroups;   // big slabs (N*C >= 64 K): ~4096 workgroups, short slab walks
-    if (sg > slabs2) sg = (int)slabs2;
-    if (sg < 1) sg = 1;
-    g.ln_spg = (int)((slabs2 + sg - 1) / sg);
-    g.ln_sg = (int)((slabs2 + g.ln_spg - 1) / g.ln_spg);
-    g.k1 = tc2_bwd_fused_ok(c1, c2, Kt, T1, T2) ? 1 : 0;
-    g.node_tiles = (N + 15) / 16;
-    {   // tc2_bwd_kernel: whole (window, node tile) items per workgroup, at most two workgroups per CU (its residency: 8 waves of ~100 VGPRs,
-        // 57 KB of LDS) -- beyond that a workgroup walks several items and keeps ONE partial block (C2: 416 items -> unchanged)
-        const long items = (long)B * g.node_tiles, cap = 2L * device_cus();
-        g.k1_wgs = (int)(items < cap ? items : cap);
-    }
-    g.k1_stride = Kt * 16 * 2 * c2 + 2 * c2;
-    if (g.k1) {   // one LayerNorm-parameter partial per window
-        g.ln_spg = T2;
-        g.ln_sg = B;
-    }
-    const long tiles1 = (rows1 + kTileRows - 1) / kTileRows;
-    g.thin = (Kt * c_in <= 4 && c0 == 64 && c1 == 16) ? 1 : 0;   // thin_tc1_bwd_kernel keeps K <= 4 rows of W_eff in registers
-    // grid-stride workgroups of align_gate_bwd (23.5 KB of LDS each: several per CU for latency hiding).  The thin
-    // first-layer kernel carries a 13 KB partial per workgroup, so fewer, longer workgroups win there
-    // (measured; 512 = 2 resident workgroups per CU at 62 KB of LDS -- a 513th would wait for a second round).
-    // (round 5: the wave-per-tile thin kernel holds 3 workgroups per CU)
-    // (pass r5-04: 256 / 384 / 512 / 768 workgroups are within noise at C2 and C3; at the 1.3 M rows of the 8192-node graph 768 -- three per
-    //  CU, its residency -- take 74 us against 81)
-    const int al_cap = g.thin ? (rows1 >= (1L << 18) && thin_wave_tiles() ? 768 : 512) : 1024;   // (768 = three per CU: the wave-per-tile form's residency; the row-tile form of STGCN_THIN=0 holds two)
-    g.al_wgs = (int)(tiles1 < al_cap ? tiles1 : al_cap);
-    long o = 0;
-    auto take = [&](long f) { long at = o; o += (f + 63) / 64 * 64; return at; };
-    g.off_ln_g = take((long)g.ln_sg * n);
-    g.off_ln_b = take((long)g.ln_sg * n);
-    g.gc_stride = (terms + 1) * 256;
-    g.gc_count = (int)slabs1;
-    g.gc_tiles_per_wg = 0;
-    if (gc_is_tiled(N, terms)) {   // ~1024 workgroups, whole groups of 4 tiles (one per wave)
-        const long tiles16 = (rows1 + 15) / 16;
-        long per = (tiles16 + 1023) / 1024;
-        per = (per + 3) / 4 * 4;
-        g.gc_tiles_per_wg = (int)per;
-        g.gc_count = (int)((tiles16 + per - 1) / per);
-    }
-    g.off_gc = take((long)g.gc_count * g.gc_stride);
-    g.al_stride = c0 * c1 + c1 + (g.thin ? 16 * 2 * c0 + 2 * c0 : 0);
-    g.off_al = take((long)g.al_wgs * g.al_stride);
-    g.w1 = wgrad_geom(rows1, Kt * c_in, 2 * c0, 0);
-    g.w1.off = take(g.w1.floats);
-    g.w2 = wgrad_geom(rows2, Kt * c1, 2 * c2, 0);
-    g.w2.off = take(g.k1 ? 0 : g.w2.floats);
-    g.off_k1 = take(g.k1 ? (long)g.k1_wgs * g.k1_stride : 0);
-    g.k3 = (need_dx && !g.thin && tc1_bwd_shape_ok(c_in, c0, c1, Kt)) ? 1 : 0;
-    g.k3_wb = 0;
-    {   // one workgroup per CU walking an equal-weight range of the (window, node tile, output step) sequence
-        const long items = (long)B * g.node_tiles;
-        long wgs = device_cus();
-        // (round 6) small batches: fewer items than compute units -- the ranges are then cut INSIDE items (at least kTc1MinSteps output steps
-        // each) instead of leaving one workgroup to walk a whole item alone: the launch is one workgroup's chain, whatever the batch
-        const long by_steps = items * (long)T / tc1_min_steps();
-        const long most = items > by_steps ? items : by_steps;
-        if (wgs > most) wgs = most;
-        g.k3_wgs = (int)wgs;
-    }
-    g.k3_stride = tc1_bwd_part_floats(c0, c_in, Kt);
-    g.off_k3 = take(g.k3 ? (long)g.k3_wgs * g.k3_stride : 0);
-    g.total = o;
-    return g;
-}
-inline int64_t bwd_partial_floats(int B, int T, int N, int c_in, int c0, int c1, int c2, int Kt, int terms, int need_dx) {
-    return bwd_geom(B, T, N, c_in, c0, c1, c2, Kt, terms, need_dx).total;
-}
-
 // ================================================================================================
 // B1a: per-ROW partial sums of g = dy_m * gamma and g * xhat (LayerNorm backward).
 //      Fully parallel streaming kernel (one float4 per thread; the C/4 lanes of a row reduce by shuffles).

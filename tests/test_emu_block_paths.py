@@ -73,3 +73,25 @@ def test_partial_arena_is_the_last_carve_of_the_workspace():
         for f, _ in type(plan)._fields_:
             if f.startswith("ws_") and f not in ("ws_part", "ws_floats"):
                 assert getattr(plan, f) <= plan.ws_part, f
+
+
+def test_plan_outside_the_partial_arena_ignores_need_dx_and_training():
+    """The weight pack of a model is planned with need_dx = 1 and training = 1 (ops.prepack_modules), the forward and backward that read it
+    with the flags of their call: every offset the pack writes to, every saved-tensor offset and every structural flag must therefore be the
+    same for the four (need_dx, training) combinations of a shape.  Only the partial-sum arena behind them (ws_part, part_floats, hence
+    ws_floats) and fused_tc1_bwd, which needs the input gradient, may differ."""
+    import itertools
+    bind("cpu")
+    free = ("ws_part", "ws_floats", "part_floats", "fused_tc1_bwd")
+    shapes = 0
+    for c_in, channels, Kt, N, B, T, gct, Ks in itertools.product(
+            (1, 2, 16, 32, 64), ((64, 16, 64), (128, 16, 64), (64, 16, 128), (128, 16, 128)), (2, 3, 4), (17, 207, 440, 600), (1, 32), (9, 12),
+            ("cheb_graph_conv", "graph_conv"), (2, 3)):
+        bcfg = ops.BlockConfig(Kt=Kt, Ks=Ks, n_vertex=N, c_in=c_in, channels=channels, act_func="glu", graph_conv_type=gct, droprate=0.5)
+        plans = [ops.query_plan(ops.make_desc(bcfg, B, T, training, need_dx)) for need_dx in (False, True) for training in (False, True)]
+        fields = [f for f, _ in type(plans[0])._fields_ if f not in free]
+        for plan in plans[1:]:
+            for f in fields:
+                assert getattr(plan, f) == getattr(plans[0], f), (f, c_in, channels, Kt, N, B, T, gct, Ks)
+        shapes += 1
+    assert shapes == 3840

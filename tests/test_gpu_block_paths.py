@@ -2,7 +2,7 @@
 once as the stage tests launch it (debug_stages on) and once as a training step does (off, partial-sum arena poisoned with NaN), the
 two runs bitwise equal in y, dx and every parameter gradient.
 
-Branches of the launchers (stgcn_amd/csrc/stgcn_capi.hip, stgcn_capi_bwd.inc, bwd_geom in stgcn_kernels_bwd.hip.h).  "old": taken by
+Branches of route_block (stgcn_amd/csrc/stgcn_route.h) and of the launchers that read it (stgcn_capi.hip, stgcn_capi_bwd.inc).  "old": taken by
 tests/test_gpu_block.py (debug_stages on only); a letter: the row of CASES that takes it.
 
 stgcn_stblock_forward
@@ -23,9 +23,9 @@ stgcn_stblock_forward
 stgcn_stblock_backward_hook
   [B1] tc2_bwd_kernel<C2, KT, training, act>: <64, 3, *, GLU / GTU> old; <64, 2>: old (x6 forward), d; <64, 4>: c, c2.  One item per
        workgroup: old; items above 2 CUs (520 on 512: eight workgroups walk two items into one partial block): e.
-       <128, 3, ..> is compiled but NEVER chosen: tc2_bwd_fused_ok bounds tc2_bwd_lds_bytes(c2, Kt, T1, T2) -- with the recompute
-       staging counted, as for bf16 -- by 81 920 bytes, and c2 = 128 needs 113 936 at the shortest T (80 656 without the staging).  Every
-       c2 = 128 block therefore takes [B2]; row f pins that through the launch log, so that a change of the bound shows up here.
+       There is no <128, ..> instance: tc2_bwd_fused_ok bounds tc2_bwd_lds_bytes(c2, Kt, T1, T2) -- with the recompute staging counted,
+       as for bf16 -- by 81 920 bytes, and c2 = 128 needs 113 936 at the shortest T (80 656 without the staging), so the predicate admits
+       c2 = 64 only.  Every c2 = 128 block takes [B2]; row f pins that through the launch log, so that a change of the bound shows up here.
   [B2] tc2 backward not fused (c2 128: old (GLU), f (GTU); T1 > 32 steps do not fit the kernel's LDS ring: m): ln_gate_bwd + tconv_bwd_weight.tc2 + tconv_bwd_data.tc2 in
        PRODUCTION
   [B3] launch_gconv_bwd: gconv_bwd2 by occupancy: old; STGCN_GCBWD2_PARTS: variants
@@ -70,7 +70,7 @@ CASES = {
     # [B1] 520 items on the 512 workgroups the cap leaves      oracle32 4.0e-6
     "e": dict(case=(64, (64, 16, 64), 3, 2, CHEB, "glu", 17, 260, 5, True), log=[("tc2_bwd_kernel<64, 3, true, 0", 512)], fused=("ln_gate_bwd", "align_gate_bwd"),
               emu=(2, 3)),
-    # c2 = 128 with GTU, eval: [F6] GTU, [B2] (tc2_bwd_kernel<128, 3, ..> is never chosen, see [B1]); [F1] / [B4] c_in 16 GTU      oracle32 1.4e-6
+    # c2 = 128 with GTU, eval: [F6] GTU, [B2] (tc2_bwd_kernel has no c2 = 128 instance, see [B1]); [F1] / [B4] c_in 16 GTU      oracle32 1.4e-6
     "f": dict(case=(16, (64, 16, 128), 3, 2, CHEB, "gtu", 21, 2, 6, False),
               log=[("ln_gate_bwd_kernel<float>", None), ("tconv_bwd_weight_kernel<", None), ("tconv_bwd_data_kernel<1, 1, 1>", None),
                    ("tc1_fwd_x6_kernel<64, 16, 3, 1>", None), ("tc1_bwd_x6_kernel<64, 16, 3, 1>", None)],
