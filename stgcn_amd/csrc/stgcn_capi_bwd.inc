@@ -192,6 +192,10 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
     BlockBwdCall c{{d, P, {}, {}, x, const_cast<float*>(saved), ws, seed, offset, offset_dev, (hipStream_t)stream}, gso_t_pad, dy, y, dx, dx_hook, {}};
     int rc = route_and_plan(d, &c.r, &c.pl);
     if (rc) return rc;
+    if (c.r.bf16 && !c.r.bf16_bwd_ok)   // up front: the launchers' STGCN_F32_ONLY would refuse the same shapes after earlier stages have run
+        return fail(STGCN_ERR_UNSUPPORTED, "stgcn_stblock_backward: no bf16 backward for c_in=%d channels=(%d, %d, %d) Kt=%d T=%d need_dx=%d "
+                    "(bf16 blocks need tc2_bwd_kernel, and tc1_bwd_kernel or the thin first layer without an input gradient)",
+                    d->c_in, d->c0, d->c1, d->c2, d->Kt, d->T, d->need_dx);
     if (!P || !x || !gso_t_pad || !dy || !saved || !ws || !G) return fail(STGCN_ERR_INVALID, "stgcn_stblock_backward: NULL buffer");
     if (!d->dy_rowstats_ready && !y) return fail(STGCN_ERR_INVALID, "stgcn_stblock_backward: y (the forward's output) is required unless dy_rowstats_ready is set");
     if (d->need_dx && !dx) return fail(STGCN_ERR_INVALID, "stgcn_stblock_backward: need_dx set but dx is NULL");

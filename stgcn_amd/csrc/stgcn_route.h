@@ -333,7 +333,15 @@ struct BlockRoute {
     bool tc1_bwd_x6;
     size_t tc1_bwd_lds;
     bool tiled_gc;           // graph conv on the tiled GEMM path
+    bool bf16_bwd_ok;        // (bf16 calls) every backward stage of this route has a bf16 instance: see bf16_backward_ok
 };
+
+// The stage-per-launch backward kernels of round 1 are fp32 only (STGCN_F32_ONLY in their launchers).  A bf16 block's backward therefore
+// needs tmp_conv2 on tc2_bwd_kernel, and tmp_conv1 on tc1_bwd_kernel or on the thin kernel -- the thin kernel only without an input
+// gradient, which the fp32 transposed conv would have to form.  stgcn_stblock_backward refuses every other bf16 route before its first launch.
+inline bool bf16_backward_ok(BwdForm tc2_bwd, BwdForm tc1_bwd, int need_dx) {
+    return tc2_bwd == BWD_FUSED && (tc1_bwd == BWD_FUSED || (tc1_bwd == BWD_THIN && !need_dx));
+}
 
 inline BlockRoute route_block(const stgcn_stblock_desc* d) {
     BlockRoute r;
@@ -402,6 +410,7 @@ inline BlockRoute route_block(const stgcn_stblock_desc* d) {
     r.thin_bwd_waves = thin_wave_tiles();
     r.tc1_bwd_x6 = x6 && g_bwd_precision == 0 && tc1_bwd_lds_bytes(d->c0, d->c_in, d->Kt, true) <= 160 * 1024;   // "bf16x6" weight-gradient products
     r.tc1_bwd_lds = tc1_bwd_lds_bytes(d->c0, d->c_in, d->Kt, r.tc1_bwd_x6);
+    r.bf16_bwd_ok = bf16_backward_ok(r.tc2_bwd, r.tc1_bwd, d->need_dx);
     return r;
 }
 

@@ -17,6 +17,7 @@ import torch
 
 from oracle import stblock_stages as st
 from stgcn_amd import _lib, ops
+from tests.block_util import param_slices
 from tests.emu_util import block_case, nonsym_gso, params_in_field_order
 
 Q = st.QuantBf16()
@@ -50,9 +51,26 @@ def err_stored(got, ref):
                 mismatch=float((d > 0).mean()))
 
 
+def _bits(a):
+    """The bit patterns of an array of float32 / float64 values, for bitwise comparisons."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
 def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso=None, seed=99, offset=3, pdrop=0.5, gc_form=None,
-                        ln_scale=None, consumer=None):
+                        ln_scale=None, consumer=None, poison=True, need_dx=None, data_seed=11, oracle=None, outputs=None):
     """Returns ({name: stored-tensor error dict}, {name: relative-to-max error of an fp32 output}).
+    poison: the arena of per-workgroup gradient partials is filled with NaN between forward and backward (as tests/block_util.py does for the
+    fp32 production sequence -- bf16 always runs that sequence): a partial block a bf16 kernel fails to write reaches a gradient as NaN
+    instead of as whatever the previous call left.  Keys prod.nan_elements (NaN among y, dx and the parameter gradients) and
+    grad_none_ok.chain_words_* (sticky / ticket words of both workspaces), bar 0.
+    need_dx: whether x requires grad (None: c_in > 1, what a model's first / later blocks do).  data_seed: seed of x and dy.
+    oracle: a dict shared between runs of one case (run_block_pair_bf16): the oracle's forward and both backwards are computed once;
+    outputs: a dict that receives y, dx and the parameter gradients (numpy) for bitwise comparisons between runs.
+    Slice keys (module docstring of tests/test_gpu_bf16_paths.py): slice.tc1_w.k<k>, slice.tc2_w.k<k>, slice.gc_w.k<k>, slice.ln_w.tail,
+    slice.ln_b.tail among the fp32 outputs (each normalised by THAT slice's max, bar F32_TOL), slice.y.tail, slice.dx.t0, slice.dx.tlast
+    among the stored tensors (err_stored over the slice, bars RMS_TOL / MAX_TOL); info.slice_ratio.<slice>: max |slice| / max |whole
+    tensor| of the PURE oracle (its own saved tensors), a condition on the inputs alone (assert_slice_ratios).
     gc_form: "poly" (slab-resident graph conv) / "recursion" (tiled path); None = whichever the plan selects.
     ln_scale = (g, b): the block's LayerNorm parameters are drawn as gamma = g * U(-1, 1), beta = b * U(-1, 1) (the
     backward rebuilds sum g * xhat from dy * (y - keep_scale * beta) with y in bf16, which amplifies y's rounding by |beta| / |gamma xhat|).
@@ -68,17 +86,26 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
         p["st_blocks.0.tc2_ln.bias"] = torch.from_numpy((ln_scale[1] * rl.uniform(-1, 1, shp)).astype(np.float32))
     if gso is None:
         gso = nonsym_gso(N, 5)
-    rs = np.random.RandomState(11)
+    need_dx = c_in > 1 if need_dx is None else bool(need_dx)
+    oracle = {} if oracle is None else oracle
+    rs = np.random.RandomState(data_seed)
     x_np = Q(rs.standard_normal((B, c_in, T, N)))                     # bf16 values, logical NCHW
     T2 = T - 2 * (Kt - 1)
     dy_np = Q(rs.standard_normal((B, channels[2], T2, N)))
     bcfg = ops.BlockConfig(Kt=Kt, Ks=Ks, n_vertex=N, c_in=c_in, channels=tuple(channels), act_func=act, graph_conv_type=gct, droprate=pdrop)
     gp, gt = ops.gso_prepare(torch.from_numpy(gso).to(dev), ops.graph_terms(bcfg))
     params = [None if t is None else t.clone().to(dev).requires_grad_(True) for t in params_in_field_order(p, "st_blocks.0.", gct)]
-    x = bf16_tensor(x_np, dev).requires_grad_(c_in > 1)
+    x = bf16_tensor(x_np, dev).requires_grad_(need_dx)
+    desc = ops.make_desc(bcfg, B, T, training, need_dx, dtype=torch.bfloat16)
+    plan = ops.query_plan(desc)
     wsc = ops.WorkspaceCache()
     y = ops.st_conv_block(x, gp, gt, bcfg, params, training, seed, offset, wsc)
     assert y.dtype == torch.bfloat16
+    if poison:
+        # the arena of per-workgroup gradient partials ONLY: the packed weights, the chain words and the row partials of a hooked
+        # LayerNorm live in front of it in the same buffer (tests/test_emu_bf16_paths.py checks that for the bf16 plans)
+        assert wsc.buf.numel() >= plan.ws_part + plan.part_floats
+        wsc.buf[plan.ws_part:plan.ws_part + plan.part_floats].fill_(float("nan"))
     hooked = None
     if consumer is None:
         y.backward(bf16_tensor(dy_np, dev))
@@ -123,13 +150,15 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
         keep = (ks > 0).astype(np.float64)
     g64 = gso.astype(np.float64)
     bp = st.block_params_np(p, "st_blocks.0.", gct, np.float64)
-    desc = ops.make_desc(bcfg, B, T, training, c_in > 1, dtype=torch.bfloat16)
-    plan = ops.query_plan(desc)
     if gc_form is None:
         gc_form = "recursion" if plan.tiled_gc else "poly"
-    y_ref, sv = st.stblock_fwd(cl(x_np), g64, bp, Kt, c_in, channels, gct, act, keep, pdrop, q=Q, gc_form=gc_form, ln_from_stored=N > 448)
-    # the same block in the fp64 statement: how far the bf16 configuration is from the reference arithmetic (reported, loosely bounded)
-    y64, sv64 = st.stblock_fwd(cl(x_np), g64, bp, Kt, c_in, channels, gct, act, keep, pdrop)
+    if "fwd" not in oracle:
+        y_ref, sv = st.stblock_fwd(cl(x_np), g64, bp, Kt, c_in, channels, gct, act, keep, pdrop, q=Q, gc_form=gc_form, ln_from_stored=N > 448)
+        # the same block in the fp64 statement: how far the bf16 configuration is from the reference arithmetic (reported, loosely bounded)
+        y64, _ = st.stblock_fwd(cl(x_np), g64, bp, Kt, c_in, channels, gct, act, keep, pdrop)
+        oracle["fwd"] = (y_ref, sv, y64, None if keep is None else keep.copy())
+    y_ref, sv, y64, keep0 = oracle["fwd"]
+    assert (keep is None) == (keep0 is None) and (keep is None or np.array_equal(keep, keep0))      # (a shared oracle: the same mask in every run)
 
     ws = wsc.buf.cpu().numpy()
     saved = torch.empty(plan.saved_floats, device=dev)
@@ -147,6 +176,10 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
     c0, c1, c2 = channels
     terms = 2 if gct == "graph_conv" else Ks
     stored, f32 = {}, {}
+    # chained launches: the sticky error word (a bounded wait gave up) of both workspaces, and ticket / finished-workgroup words re-armed
+    for nm, buf in (("autograd", wsc.buf), ("direct", ws2)):
+        cw = buf[plan.ws_chain:plan.ws_chain + 4].view(torch.int32).cpu().numpy()
+        f32[f"grad_none_ok.chain_words_{nm}"] = float(abs(cw[:3]).sum())
     if hooked is not None:
         f32["grad_none_ok.hook_epilogue_used"] = 0.0 if hooked else 1.0      # (tolerance 0: the consumer's epilogue wrote the row partials, no ln_bwd_rowstats launch)
     if not plan.recompute_tc1:
@@ -163,6 +196,9 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
     stored["fwd.y"] = err_stored(cl(bf16_numpy(y)), y_ref)
     stored["fwd.y_vs_fp64"] = err_stored(cl(bf16_numpy(y)), y64)          # (reported; bounded loosely below)
     f32["fwd.mean"] = float(np.abs(svn[plan.sv_mean:plan.sv_mean + B * T2].reshape(B, T2) - sv["mean"]).max() / max(1e-30, np.abs(sv["mean"]).max() + 1e-3))
+    # the same error in units of the slab's standard deviation: a slab whose mean happens to lie near zero does not inflate it (bar: fwd.rstd's)
+    f32["fwd.mean_over_std"] = float((np.abs(svn[plan.sv_mean:plan.sv_mean + B * T2].reshape(B, T2) - sv["mean"]) * sv["rstd"]).max())
+    f32["info.ref_abs_mean_max"], f32["info.ref_std_min"] = float(np.abs(sv["mean"]).max()), float((1.0 / sv["rstd"]).min())
     f32["fwd.rstd"] = float(np.abs(svn[plan.sv_rstd:plan.sv_rstd + B * T2].reshape(B, T2) / sv["rstd"] - 1).max())
     f32["fwd.y_repeat_bitwise"] = float((y2.view(torch.int16) != y.detach().permute(0, 2, 3, 1).contiguous().view(torch.int16)).sum().item())
     # Backward: checked on the HIP path's OWN saved tensors ("teacher forcing").  ReLU is discontinuous: where a stored G sits on the
@@ -180,17 +216,26 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
     svh["y"] = cl(bf16_numpy(y))
     svh["mean"] = svn[plan.sv_mean:plan.sv_mean + B * T2].reshape(B, T2).astype(np.float64)
     svh["rstd"] = svn[plan.sv_rstd:plan.sv_rstd + B * T2].reshape(B, T2).astype(np.float64)
-    stages = {}
-    dx_ref, g_ref = st.stblock_bwd(cl(dy_np), svh, g64, bp, Kt, c_in, channels, gct, act, pdrop, need_dx=c_in > 1, q=Q, gc_form=gc_form,
-                                   stages=stages)
+    import hashlib
+    digest = lambda *arrs: hashlib.sha1(b"".join(np.ascontiguousarray(a).tobytes() for a in arrs)).hexdigest()
+    fkey = ("forced", digest(svh["U1"], svh["S1"], *svh["Xs"], svh["G"], svh["mean"], svh["rstd"], svh["y"], dy_np))      # (the forced oracle depends on what the library saved)
+    if fkey not in oracle:
+        stages = {}
+        dx_ref, g_ref = st.stblock_bwd(cl(dy_np), svh, g64, bp, Kt, c_in, channels, gct, act, pdrop, need_dx=need_dx, q=Q, gc_form=gc_form,
+                                       stages=stages)
+        oracle[fkey] = (dx_ref, g_ref, stages)
+    dx_ref, g_ref, stages = oracle[fkey]
     # How much of the backward the teacher forcing hides: the ReLU-mask flip rate between the two forwards, and the
     # gradients against the PURE oracle (its own saved tensors, no forcing), bounded in rms: a flipped mask element changes the gradient
     # entering the graph conv by O(1) there, so the un-forced error is ~sqrt(flip rate) in rms, not a kernel defect.
     flip = float(((svh["G"] > 0) != (np.asarray(sv["G"]) > 0)).mean())
     f32["relu_flip_rate"] = flip
-    dx_u, g_u = st.stblock_bwd(cl(dy_np), sv, g64, bp, Kt, c_in, channels, gct, act, pdrop, need_dx=c_in > 1, q=Q, gc_form=gc_form)
+    ukey = ("unforced", digest(dy_np))
+    if ukey not in oracle:
+        oracle[ukey] = st.stblock_bwd(cl(dy_np), sv, g64, bp, Kt, c_in, channels, gct, act, pdrop, need_dx=need_dx, q=Q, gc_form=gc_form)
+    dx_u, g_u = oracle[ukey]
     rms = lambda a: float(np.sqrt((np.asarray(a, np.float64) ** 2).mean()))
-    if c_in > 1:
+    if need_dx:
         f32["unforced_rms.dx"] = rms(cl(bf16_numpy(x.grad)) - dx_u) / max(1e-30, rms(dx_u))
     worst = 0.0
     for name, prm in zip(_lib.PARAM_FIELDS, params):
@@ -199,9 +244,13 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
     f32["unforced_rms.param_grads_worst"] = worst
     stored["bwd.dYg"] = err_stored(seg_bf16(ws, plan.ws_dYg, (B, T1, N, c1)), stages["dYg"])
     stored["bwd.dA"] = err_stored(seg_bf16(ws, plan.ws_dA, (B, T1, N, c1)), stages["dA"])
-    if c_in > 1:
-        stored["bwd.dx"] = err_stored(cl(bf16_numpy(x.grad)), dx_ref)
+    dx = cl(bf16_numpy(x.grad)) if need_dx else None
+    if need_dx:
+        stored["bwd.dx"] = err_stored(dx, dx_ref)
+    else:
+        f32["grad_none_ok.dx"] = 0.0 if x.grad is None else 1.0
     rel = lambda got, ref: float(np.abs(got - ref).max() / max(1e-30, np.abs(ref).max()))
+    got, shaped, shaped_u = {}, {}, {}
     for name, prm in zip(_lib.PARAM_FIELDS, params):
         ref = g_ref[name]
         if prm is None:
@@ -210,10 +259,87 @@ def run_block_case_bf16(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training
             f32["grad_none_ok." + name] = 0.0 if prm.grad is None else 1.0
             continue
         f32["grad." + name] = rel(prm.grad.cpu().numpy().astype(np.float64), ref.reshape(prm.shape)) if prm.grad is not None else float("inf")
+        if prm.grad is not None:
+            got[name], shaped[name], shaped_u[name] = prm.grad.cpu().numpy(), ref.reshape(prm.shape), g_u[name].reshape(prm.shape)
+    # ---- slices: a whole-tensor maximum hides a wrong tap / term / ragged tile / edge step.  Every element of a tap or term slice sums over the
+    # same rows as the whole tensor, every ln_w element over the same B * T2 slabs, tail or not: the per-element statistics are those the
+    # whole-tensor bars were stated for, only the normaliser shrinks -- and info.slice_ratio.* bounds by how much (assert_slice_ratios)
+    amax = lambda a: float(np.abs(a).max())
+    y_cl = svh["y"]
+    for key, name, idx in param_slices(shaped, Kt, N, gct):
+        f32[key] = rel(got[name][idx].astype(np.float64), shaped[name][idx]) if name in got else float("inf")
+        if name in got:
+            f32["info.slice_ratio." + key[len("slice."):]] = amax(shaped_u[name][idx]) / max(1e-30, amax(shaped_u[name]))
+    tail = N - N % 16
+    if N % 16:
+        stored["slice.y.tail"] = err_stored(y_cl[:, :, tail:], y_ref[:, :, tail:])
+        f32["info.slice_ratio.y.tail"] = amax(y_ref[:, :, tail:]) / max(1e-30, amax(y_ref))
+    if need_dx:
+        for nm, t in (("t0", 0), ("tlast", T - 1)):
+            stored[f"slice.dx.{nm}"] = err_stored(dx[:, t], dx_ref[:, t])
+            f32[f"info.slice_ratio.dx.{nm}"] = amax(dx_u[:, t]) / max(1e-30, amax(dx_u))
+    outs = {"y": y_cl.astype(np.float32), **({"dx": dx.astype(np.float32)} if need_dx else {}), **{"grad." + k: v for k, v in got.items()}}
+    if poison:
+        f32["prod.nan_elements"] = float(sum(int(np.isnan(v).sum()) for v in outs.values()))
+    if outputs is not None:
+        outputs.update(outs)
     return stored, f32
 
 
-def assert_bf16_errors(stored, f32):
+def run_block_pair_bf16(dev, *case, on_half=None, **kw):
+    """One case twice with a shared oracle: the partial-sum arena as the forward left it ("clean"), then filled with NaN ("poisoned").  Returns
+    the poisoned run's keys, the clean run's as clean.<key>, and prod.bitwise_clean_vs_poisoned: elements of y, dx and all parameter
+    gradients whose bits differ between the two runs (bar 0: the bf16 counterpart of block_util's prod.bitwise_vs_debug)."""
+    oracle, out_c, out_p = {}, {}, {}
+    on_half = on_half or (lambda half, edge: None)      # (the launch-log test marks where each half's launches begin and end)
+    on_half("clean", "begin")
+    stored_c, f32_c = run_block_case_bf16(dev, *case, poison=False, oracle=oracle, outputs=out_c, **kw)
+    on_half("clean", "end")
+    on_half("poisoned", "begin")
+    stored, f32 = run_block_case_bf16(dev, *case, poison=True, oracle=oracle, outputs=out_p, **kw)
+    on_half("poisoned", "end")
+    stored.update({"clean." + k: v for k, v in stored_c.items()})
+    f32.update({"clean." + k: v for k, v in f32_c.items() if not k.startswith("info.")})
+    assert out_c.keys() == out_p.keys()
+    f32["prod.bitwise_clean_vs_poisoned"] = float(sum(int((_bits(out_c[k]) != _bits(out_p[k])).sum()) for k in out_c))
+    return stored, f32
+
+
+def slice_ratios(f32):
+    return {k[len("info.slice_ratio."):]: v for k, v in f32.items() if k.startswith("info.slice_ratio.")}
+
+
+def assert_slice_ratios(f32, floor=0.25):
+    """The condition under which the slice keys may share the whole-tensor bars: every slice's max |ref| is at least `floor` of its whole
+    tensor's (the oracle alone, on the case's inputs).  A row that misses it gets another data seed, never another bar."""
+    r = slice_ratios(f32)
+    assert r and min(r.values()) >= floor, {k: v for k, v in r.items() if v < floor} or "no slice keys"
+
+
+def bf16_bar(k):
+    """The bar an fp32-output key is held to."""
+    if k.startswith("clean."):
+        k = k[len("clean."):]
+    # (LayerNorm statistics are fp32 sums, but of values downstream of bf16 tensors in which a few elements differ by one ulp)
+    # relu_flip_rate: measured 0 - 3e-4 (elements of G within one bf16 ulp of zero); un-forced gradients: rms error <= 5 % (measured ~1 %)
+    if k.startswith("grad_none_ok") or k.endswith("bitwise") or k in ("prod.nan_elements", "prod.bitwise_clean_vs_poisoned"):
+        return 0.0
+    if k.startswith("info."):
+        return float("inf")
+    return (1e-3 if k in ("fwd.mean", "fwd.rstd", "fwd.mean_over_std") else 2e-3 if k == "relu_flip_rate" else
+            5e-2 if k.startswith("unforced_rms") else F32_TOL)
+
+
+def report_bf16_paths(stored, f32, label, path):
+    """Appends one JSON line per row with every key to `path` (how profiles/bf16_block_stage_errors.md is made: tools/bf16_stage_report.py)."""
+    import json
+    with open(path, "a") as fh:
+        fh.write(json.dumps({"case": label, "f32": f32, "stored": stored}) + "\n")
+
+
+def assert_bf16_errors(stored, f32, report_only=()):
+    """report_only: keys that are reported but not held to their bar (fwd.mean of a row with fewer than 4 (b, t2) slabs, whose normaliser
+    is a maximum over that few |mean|: such a row is held to fwd.mean_over_std, tests/test_gpu_bf16_paths.py)."""
     import json, os
     if os.environ.get("STGCN_BF16_REPORT"):      # (GPU passes: the measured flip rates / un-forced errors go into profiles/)
         with open(os.environ["STGCN_BF16_REPORT"], "a") as fh:
@@ -221,18 +347,16 @@ def assert_bf16_errors(stored, f32):
                                  "stored_rms": {k: round(v["rms"], 6) for k, v in stored.items()}}) + "\n")
     bad = {}
     for k, e in stored.items():
-        if k.endswith("_vs_fp64"):
+        if k.endswith("_vs_fp64"):      # (clean.* keys: the same bars)
             if not (e["rms"] <= 3e-2):          # bf16 storage + bf16 operands vs exact arithmetic: ~1 % rms on unit-variance outputs
                 bad[k] = e
             continue
         if not (e["rms"] <= RMS_TOL and e["max"] <= MAX_TOL):
             bad[k] = e
     for k, v in f32.items():
-        # (LayerNorm statistics are fp32 sums, but of values downstream of bf16 tensors in which a few elements differ by one ulp)
-        # relu_flip_rate: measured 0 - 3e-4 (elements of G within one bf16 ulp of zero); un-forced gradients: rms error <= 5 % (measured ~1 %)
-        tol = (0.0 if (k.startswith("grad_none_ok") or k.endswith("bitwise")) else 1e-3 if k in ("fwd.mean", "fwd.rstd") else
-               2e-3 if k == "relu_flip_rate" else 5e-2 if k.startswith("unforced_rms") else F32_TOL)
-        if not (v <= tol):
+        if k in report_only or (k.startswith("clean.") and k[len("clean."):] in report_only):
+            continue
+        if not (v <= bf16_bar(k)):
             bad[k] = v
     assert not bad, f"out of tolerance: {bad}\nstored: {stored}\nf32: {f32}"
 

@@ -61,6 +61,20 @@ def cl(a):
     return np.ascontiguousarray(a.transpose(0, 2, 3, 1))
 
 
+def param_slices(ref, Kt, N, gct):
+    """(key, parameter name, index) of every parameter-gradient slice the harnesses measure on its own (tests/bf16_util.py shares it):
+    tap k of the two temporal convs, Chebyshev term k of the graph conv, the LayerNorm rows of the last ragged 16-node tile."""
+    for name in ("tc1_w", "tc2_w"):
+        for k in range(Kt):
+            yield f"slice.{name}.k{k}", name, (slice(None), slice(None), k)
+    if gct == "cheb_graph_conv":
+        for k in range(ref["gc_w"].shape[0]):
+            yield f"slice.gc_w.k{k}", "gc_w", (k,)
+    if N % 16:
+        for k in ("ln_w", "ln_b"):
+            yield f"slice.{k}.tail", k, (slice(N - N % 16, None),)
+
+
 def slice_metrics(got, ref, dx, dx_ref, y, y_ref, Kt, N, gct, prefix=""):
     """{key: error} of the gradients `got` against `ref` (dicts keyed like st.block_params_np, arrays shaped like the parameters; None =
     no gradient), dx and y (channels-last; None = absent): per tensor, per tap, per Chebyshev term, over the ragged node tile and over
@@ -69,16 +83,10 @@ def slice_metrics(got, ref, dx, dx_ref, y, y_ref, Kt, N, gct, prefix=""):
     for k, r in ref.items():
         if r is not None and got.get(k) is not None:
             err[f"{prefix}grad.{k}"] = rel(got[k], r)
-    for name in ("tc1_w", "tc2_w"):
-        for k in range(Kt):
-            err[f"{prefix}slice.{name}.k{k}"] = rel(got[name][:, :, k], ref[name][:, :, k])
-    if gct == "cheb_graph_conv":
-        for k in range(ref["gc_w"].shape[0]):
-            err[f"{prefix}slice.gc_w.k{k}"] = rel(got["gc_w"][k], ref["gc_w"][k])
+    for key, name, idx in param_slices(ref, Kt, N, gct):
+        err[prefix + key] = rel(got[name][idx], ref[name][idx])
     tail = N - N % 16
     if N % 16:
-        for k in ("ln_w", "ln_b"):
-            err[f"{prefix}slice.{k}.tail"] = rel(got[k][tail:], ref[k][tail:])
         if y is not None:
             err[f"{prefix}slice.y.tail"] = float(np.abs(y[:, :, tail:].astype(np.float64) - y_ref[:, :, tail:]).max())
     if dx_ref is not None and dx is not None:

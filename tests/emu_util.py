@@ -23,6 +23,15 @@ def nonsym_gso(n, seed):
     return (a / max(1.0, np.abs(np.linalg.eigvals(a)).max())).astype(np.float32)
 
 
+def sym_gso(n, seed):
+    """A symmetric operator with its spectrum in [-1, 1], like the rescaled Laplacian a model feeds the Chebyshev recursion: T_k of it
+    has norm <= 1, so no term of a Ks = 5 graph conv dwarfs the others (a non-normal operator of spectral radius 1 lets T_4 grow)."""
+    rs = np.random.RandomState(seed)
+    a = rs.uniform(-1, 1, (n, n)) * (rs.uniform(size=(n, n)) < 0.6)
+    a = (a + a.T) / 2
+    return (a / np.abs(np.linalg.eigvalsh(a)).max()).astype(np.float32)
+
+
 def block_case(c_in, channels, Kt, Ks, gct, act, N, B, T, seed=3):
     """Parameters (reference state_dict names, fp32 torch) + numpy views for the stage oracle."""
     cfg = orc.OracleConfig(Kt=Kt, Ks=Ks, n_his=T, act_func=act, graph_conv_type=gct, droprate=0.5,

@@ -125,21 +125,9 @@ def run(name, dev=DEV, label=None, case=None, on_half=None):
 
 def log_spans(name):
     """STGCN_BLOCK_LOG_SPANS=<file> (set by tests/test_gpu_block_variants.py beside STGCN_LAUNCH_LOG): the byte range of the launch log
-    each half of each row wrote, one JSON line per half."""
-    path, log = os.environ.get("STGCN_BLOCK_LOG_SPANS"), os.environ.get("STGCN_LAUNCH_LOG")
-    if not path or not log:
-        return None
-    import json
-    size = lambda: os.path.getsize(log) if os.path.exists(log) else 0      # (the library flushes every line)
-    state = {}
-
-    def on_half(half, edge):
-        if edge == "begin":
-            state[half] = size()
-        else:
-            with open(path, "a") as fh:
-                fh.write(json.dumps({"row": name, "half": half, "lo": state[half], "hi": size()}) + "\n")
-    return on_half
+    each half of each row wrote, one JSON line per half (tests/launch_log_util.py)."""
+    from tests.launch_log_util import span_recorder
+    return span_recorder(name, "STGCN_BLOCK_LOG_SPANS")
 
 
 @pytest.mark.parametrize("name", list(CASES))

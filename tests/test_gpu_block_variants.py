@@ -8,13 +8,11 @@ neither MFMA hardware nor real wave scheduling.
 Every setting needs a fresh process: one child pytest at a time, each under its own time limit; a child that fails, dies or runs out of
 time fails the test and is not started again.
 """
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from tests.launch_log_util import check_rows_take_their_branch, passed, read_launches, run_child
 from tests.test_gpu_block_paths import CASES
 
 pytestmark = pytest.mark.gpu
@@ -22,21 +20,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = "tests/test_gpu_block.py"
 PATHS = "tests/test_gpu_block_paths.py"
 DEBUG_LAUNCHES = ("ln_gate_bwd", "align_gate_bwd")
-
-
-def run_child(env_extra, files, k, timeout=300):
-    env = dict(os.environ, **env_extra)
-    r = subprocess.run([sys.executable, "-m", "pytest", *files, "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", "-k", k],
-                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and " skipped" not in r.stdout, r.stdout[-2000:]
-    return r.stdout
-
-
-def passed(stdout):
-    import re
-    m = re.search(r"(\d+) passed", stdout)
-    return int(m.group(1)) if m else 0
 
 
 def small_rows(*ids):
@@ -47,28 +30,10 @@ def path_rows(*names):
     return " or ".join(f"test_block_paths[{n}]" for n in names)
 
 
-def parse_launch_log(log_bytes, spans):
-    """{(row, half): [(label, kernel text, workgroups)]} from the launch log and the byte spans test_gpu_block_paths.log_spans recorded."""
-    out = {}
-    for s in spans:
-        lines = log_bytes[s["lo"]:s["hi"]].decode().splitlines()
-        rows = []
-        for ln in lines:
-            label, kernel, wgs, _threads = ln.split("\t")
-            rows.append((label.split("@")[0], kernel, int(wgs)))
-        out[(s["row"], s["half"])] = rows
-    return out
-
-
 def check_launch_log(launches):
     """The assertions of test_every_row_takes_its_branch on a parsed log (also run on an emulator log by the CPU suite's scratch checks)."""
+    check_rows_take_their_branch(launches, CASES, ("debug", "prod"))
     for name, row in CASES.items():
-        for half in ("debug", "prod"):
-            got = launches[(name, half)]
-            assert got, (name, half)
-            for text, wgs in row["log"]:
-                hit = [g for g in got if text in g[1] and (wgs is None or g[2] == wgs)]
-                assert hit, f"row {name} ({half}): no launch of '{text}' with {wgs} workgroups in {got}"
         labels_debug = [g[0] for g in launches[(name, "debug")]]
         labels_prod = [g[0] for g in launches[(name, "prod")]]
         for lab in row["fused"]:
@@ -83,7 +48,7 @@ def test_every_row_takes_its_branch(tmp_path):
     log, spans = tmp_path / "launch.log", tmp_path / "spans.jsonl"
     out = run_child({"STGCN_LAUNCH_LOG": str(log), "STGCN_BLOCK_LOG_SPANS": str(spans)}, [PATHS], "test_block_paths", timeout=900)
     assert passed(out) == len(CASES), out[-2000:]
-    launches = parse_launch_log(log.read_bytes(), [json.loads(ln) for ln in spans.read_text().splitlines()])
+    launches = read_launches(log, spans)
     assert len(launches) == 2 * len(CASES)
     check_launch_log(launches)
 
