@@ -282,7 +282,8 @@ int stgcn_stblock_backward(const stgcn_stblock_desc* desc, const stgcn_stblock_p
  *      and y is the consumer's own input.  stgcn_stblock_ln_hook describes the LayerNorm of a block's forward call (same desc / params /
  *      y / ws / seed / offset as that call); hand it to the backward call of the module that consumed the block's output
  *      (..._backward_hook below) and set desc.dy_rowstats_ready = 1 in the block's own backward call.  A NULL hook reproduces
- *      stgcn_*_backward.                                                                                                        */
+ *      stgcn_*_backward.  With STGCN_FUSE lacking 4 stgcn_stblock_ln_hook returns a hook whose rowstat is NULL: a consumer handed
+ *      it writes nothing, and the caller must leave dy_rowstats_ready at 0.                                                    */
 typedef struct stgcn_ln_hook {
     float* rowstat;            /* [B*T2*N][2] destination (inside the block's ws)                                     */
     const float* y;            /* [B*T2*N][c2] the block's output (dtype below), BIT FOR BIT as the forward wrote it: in training

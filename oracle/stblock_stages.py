@@ -297,6 +297,23 @@ def ln_dropout_bwd(dy, H, gamma, mean, rstd, keep, p, y_stored=None, beta=None):
     return dH, (dym * xhat).sum(axis=(0, 1)), dym.sum(axis=(0, 1))
 
 
+def ln_rowstats(dy, H, gamma, mean, rstd, keep, p, y_stored=None, beta=None):
+    """The LayerNorm-backward row partials (sum_c g, sum_c g * xhat), each [B, T2, N], with g = keep * dy * gamma / (1 - p): what
+    ln_bwd_rowstats_kernel and the stgcn_ln_hook epilogues of a consumer write per (b, t2, n) row, in the dtype of dy.
+    y_stored / beta: the second sum the way those kernels form it, without xhat, from the block's stored output
+    y = mask * (xhat * gamma + beta):  sum_kept dy * (y - beta / (1 - p))."""
+    ks = 1.0 if keep is None else 1.0 / (1.0 - p)
+    kept = 1.0 if keep is None else keep
+    ks = dy.dtype.type(ks)
+    sg = (dy * kept * ks * gamma).sum(axis=-1)
+    if y_stored is None:
+        xhat = (H - mean[..., None, None]) * rstd[..., None, None]
+        sgx = (dy * kept * ks * gamma * xhat).sum(axis=-1)
+    else:
+        sgx = (dy * kept * (y_stored - ks * beta)).sum(axis=-1)
+    return sg, sgx
+
+
 # ----------------------------------------------------------------------------- whole block
 def block_params_np(p, prefix, graph_conv_type, dtype):
     g = lambda k: (p[prefix + k].detach().cpu().numpy().astype(dtype) if (prefix + k) in p else None)

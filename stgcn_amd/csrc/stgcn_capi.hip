@@ -1170,6 +1170,7 @@ int stgcn_stblock_ln_hook(const stgcn_stblock_desc* d, const stgcn_stblock_param
     if (rc) return rc;
     if (!P || !P->ln_w || !P->ln_b || !y || !ws || !h) return fail(STGCN_ERR_INVALID, "stgcn_stblock_ln_hook: NULL argument");
     memset(h, 0, sizeof(*h));
+    if (!(fuse_mask() & FUSE_ROWSTATS)) return STGCN_OK;   // STGCN_FUSE without 4: a hook without a destination -- no consumer writes partials, callers must not set dy_rowstats_ready
     h->rowstat = ws + pl.ws_rowstat_b; h->y = y; h->gamma = P->ln_w; h->beta = P->ln_b;
     h->N = d->N; h->C = d->c2; h->training = d->training; h->droprate = d->droprate; h->dtype = d->dtype;
     h->seed = seed; h->offset = offset; h->offset_dev = offset_dev;

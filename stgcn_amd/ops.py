@@ -619,8 +619,9 @@ class _STBlockFn(torch.autograd.Function):
             hk = _lib.LnHook()
             L.check(L.dll.stgcn_stblock_ln_hook(C.byref(desc), C.byref(pst), y.data_ptr(), ws.data_ptr(), seed, offset, _optr(offset_dev),
                                                 C.byref(hk)), "stgcn_stblock_ln_hook")
-            ctx.own_hook = LnHookState(hk, (ws, ps, offset_dev))      # (y itself is pinned by the _ln_hooks entry)
-            _offer_ln_hook(y, ctx.own_hook)
+            if hk.rowstat:      # (NULL: the library forms no row partials in consumers -- STGCN_FUSE without bit 4 -- so nothing is offered)
+                ctx.own_hook = LnHookState(hk, (ws, ps, offset_dev))      # (y itself is pinned by the _ln_hooks entry)
+                _offer_ln_hook(y, ctx.own_hook)
         ctx.save_for_backward(x_cl, saved, gso_t_pad, y, *[p for p in params if p is not None])
         ctx.param_present = [p is not None for p in params]
         ctx.cfg, ctx.training, ctx.seed, ctx.offset, ctx.wsc, ctx.ws = cfg, training, seed, offset, wsc, ws

@@ -2,11 +2,57 @@
 
     STGCN_BLOCK_REPORT=block_report.jsonl python -m pytest tests/test_gpu_block_paths.py -q -m gpu
     python tools/block_stage_report.py block_report.jsonl > profiles/block_stage_errors.md
+
+and profiles/block_hook_errors.md from those of tests/test_gpu_block_hooks.py (the oracle32.hook.* columns from the emulator run of the
+same table, tests/test_emu_block_hooks.py, which measures them on the CPU):
+
+    STGCN_BLOCK_REPORT=hooks_gpu.jsonl python -m pytest tests/test_gpu_block_hooks.py -q -m gpu -k test_block_hooks
+    STGCN_BLOCK_REPORT=hooks_cpu.jsonl python -m pytest tests/test_emu_block_hooks.py -q -k test_block_hooks_on_the_emulator
+    python tools/block_stage_report.py --hooks hooks_gpu.jsonl hooks_cpu.jsonl > profiles/block_hook_errors.md
 """
 import json
 import sys
 
 f = lambda v: "%.1e" % v
+
+
+def hook_report(gpu_path, cpu_path):
+    from tests.block_util import bar
+    gpu = [json.loads(l) for l in open(gpu_path)]
+    cpu = {json.loads(l)["case"].replace(" emu", ""): json.loads(l) for l in open(cpu_path)} if cpu_path else {}
+    out = ["# LayerNorm hook epilogues of fp32 blocks: per-row errors on the MI355X", "",
+           "Measured by `tests/test_gpu_block_hooks.py` (harness `tests/block_util.py`, consumer mode; table made by",
+           "`tools/block_stage_report.py --hooks`).  Row names, the pair P -> Q of each row and the branch it reaches: the `CASES` table of that",
+           "file.  `debug` / `prod`: the two launch sequences, as in `profiles/block_stage_errors.md`.  `worst`: the key that comes closest to",
+           "its bar (value / bar; keys with bar 0 are all 0 unless listed under the table), with its value.  `rowstat g` / `gx`: the row partials",
+           "Q wrote against the float64 sums, max error / max |ref| (bar 1e-3); `vs own pass`: against the partials P's own",
+           "`ln_bwd_rowstats_kernel` writes for the same dy (bar 1e-3); `NaN`: partials the backward left unwritten; `dy bits`: elements of Q's input",
+           "gradient that differ from Q run without a hook; `launches`: |observed - expected| `ln_bwd_rowstats` launches (bars 0).  `oracle32 g / gx`:",
+           "the same sums formed in `np.float32` the way the kernels form them, measured on the CPU (`tests/test_emu_block_hooks.py`; the rows",
+           "`big` and `many` are measured in the GPU run, at their full size), bar 2.5e-4.", "",
+           "| row | worst | rowstat g | rowstat gx | vs own pass g / gx | NaN | dy bits | launches | bitwise | oracle32 g / gx |",
+           "|---|---|---|---|---|---|---|---|---|---|"]
+    nonzero = []
+    for d in gpu:
+        for half, pre in (("debug", ""), ("prod", "prod.")):
+            e = {k[len(pre):]: v for k, v in d.items() if k != "case" and (k.startswith("prod.") == bool(pre))}
+            ratios = [(v / bar(k), k, v) for k, v in e.items() if 0 < bar(k) < float("inf") and not k.startswith("oracle32.")]
+            _, wk, wv = max(ratios)
+            nonzero += [(d["case"], half, k, v) for k, v in e.items() if bar(k) == 0 and v != 0]
+            o = cpu.get(d["case"]) if (d["case"] in cpu and "big" != d["case"] and "many" != d["case"]) else d
+            out.append("| %s %s | `%s` %s | %s | %s | %s / %s | %d | %d | %d | %s | %s |" % (
+                d["case"], half, wk, f(wv), f(e["hook.rowstat_g"]), f(e["hook.rowstat_gx"]), f(e["hook.rowstat_vs_own_pass_g"]),
+                f(e["hook.rowstat_vs_own_pass_gx"]), e["hook.rowstat_nan"], e["hook.dy_bitwise_vs_unhooked"], e["grad_none_ok.hook_launches"],
+                ("%d" % d["prod.bitwise_vs_debug"]) if pre else "",
+                "" if pre else "%s / %s" % (f(o["oracle32.hook.rowstat_g"]), f(o["oracle32.hook.rowstat_gx"]))))
+    out += ["", "Every key with bar 0 is 0 on every row." if not nonzero else "KEYS WITH BAR 0 THAT ARE NOT 0: %s" % nonzero]
+    print("\n".join(out))
+
+
+if sys.argv[1] == "--hooks":
+    sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
+    hook_report(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
+    sys.exit(0)
 rows = [json.loads(l) for l in open(sys.argv[1])]
 out = ["# ST block: per-row, per-stage errors on the MI355X", "",
        "Measured by `tests/test_gpu_block_paths.py` (harness `tests/block_util.py`, table made by `tools/block_stage_report.py`) against the",
