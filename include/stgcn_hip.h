@@ -302,7 +302,8 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* desc, const stgcn_stbl
                                 const stgcn_stblock_grads* grads, float* dx, uint64_t seed, uint64_t offset,
                                 const uint64_t* offset_dev, const stgcn_ln_hook* dx_hook, void* stream);
 
-/* out[e] = 0 or 1/(1-p): the keep-scale the forward applies to element e of y (n multiple of 4).     */
+/* out[e] = 0 or 1/(1-p): the keep-scale the forward applies to element e of y (n multiple of 4).
+ * droprate outside [0, 1) (NaN included) -> STGCN_ERR_INVALID, like the block and head descriptors.  */
 int stgcn_dropout_mask(float* out, int64_t n, float droprate, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                        void* stream);
 

@@ -130,7 +130,7 @@ int check_desc(const stgcn_stblock_desc* d) {
     if (d->act != STGCN_ACT_GLU && d->act != STGCN_ACT_GTU) return fail(STGCN_ERR_INVALID, "act must be glu or gtu");
     if (d->graph_conv != STGCN_GC_CHEB && d->graph_conv != STGCN_GC_KIPF) return fail(STGCN_ERR_INVALID, "bad graph_conv enum");
     if (d->T - 2 * (d->Kt - 1) < 1) return fail(STGCN_ERR_INVALID, "T=%d too short for two Kt=%d temporal convs", d->T, d->Kt);
-    if (d->droprate < 0.f || d->droprate >= 1.f) return fail(STGCN_ERR_INVALID, "droprate must be in [0, 1)");
+    if (!(d->droprate >= 0.f && d->droprate < 1.f)) return fail(STGCN_ERR_INVALID, "droprate must be in [0, 1)");   // (this form refuses NaN too)
     if (!(d->c0 == 64 || d->c0 == 128) || !(d->c2 == 64 || d->c2 == 128))
         return fail(STGCN_ERR_UNSUPPORTED, "temporal-conv output channels must be 64 or 128 (got c0=%d c2=%d)", d->c0, d->c2);
     if (d->c1 != 16) return fail(STGCN_ERR_UNSUPPORTED, "graph-conv channels c1 must be 16 (got %d)", d->c1);
@@ -1157,6 +1157,8 @@ int stgcn_gso_prepare(const float* gso, int32_t N, int32_t terms, float* gso_pad
 
 int stgcn_dropout_mask(float* out, int64_t n, float droprate, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream) {
     if (!out || n < 0 || (n & 3)) return fail(STGCN_ERR_INVALID, "stgcn_dropout_mask: n must be a non-negative multiple of 4");
+    // at p = 1 the keep scale is inf and a draw of 0xFFFFFFFF is still kept (drop_thresh clamps to 2^32 - 1); NaN fails both compares
+    if (!(droprate >= 0.f && droprate < 1.f)) return fail(STGCN_ERR_INVALID, "stgcn_dropout_mask: droprate must be in [0, 1)");
     if (n == 0) return STGCN_OK;
     STGCN_LAUNCH("dropout_mask", (hipStream_t)stream, dropout_mask_kernel, dim3(cdiv(n / 4, kThreads)), dim3(kThreads), 0, out,
                  (long)(n / 4), seed, offset, offset_dev, drop_thresh(droprate), 1.0f / (1.0f - droprate));

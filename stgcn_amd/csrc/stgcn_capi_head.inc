@@ -15,7 +15,7 @@ int head_check(const stgcn_outblock_desc* d) {
     if (d->B < 1 || d->T < 1 || d->N < 1 || d->c_in < 1 || d->Ko < 1) return fail(STGCN_ERR_INVALID, "B/T/N/c_in/Ko must be positive");
     if (d->T < d->Ko) return fail(STGCN_ERR_INVALID, "T=%d shorter than Ko=%d", d->T, d->Ko);
     if (d->act != STGCN_ACT_GLU && d->act != STGCN_ACT_GTU) return fail(STGCN_ERR_INVALID, "act must be glu or gtu");
-    if (d->droprate < 0.f || d->droprate >= 1.f) return fail(STGCN_ERR_INVALID, "droprate must be in [0, 1)");
+    if (!(d->droprate >= 0.f && d->droprate < 1.f)) return fail(STGCN_ERR_INVALID, "droprate must be in [0, 1)");   // (this form refuses NaN too)
     if (!(d->c0 == 64 || d->c0 == 128)) return fail(STGCN_ERR_UNSUPPORTED, "output-head conv channels must be 64 or 128 (got %d)", d->c0);
     if (d->c1 != 128) return fail(STGCN_ERR_UNSUPPORTED, "output-head fc1 width must be 128 (got %d)", d->c1);
     if (d->c_end != 1) return fail(STGCN_ERR_UNSUPPORTED, "end_channel must be 1 (got %d)", d->c_end);

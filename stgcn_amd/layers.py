@@ -34,7 +34,26 @@ class DropoutStream:
     Eager mode: every training forward of every block consumes one host-side offset, so masks never
     repeat.  Graph mode (``use_device_counter``): kernel arguments are frozen inside a captured hipGraph, so
     the running part of the offset lives in a device int64 that the captured step bumps (``advance``);
-    each block adds its own static site id.  The trainer gives each data-parallel rank its own seed."""
+    each block adds its own static site id.  The trainer gives each data-parallel rank its own seed.
+
+    Where every site draws (pinned by tests/test_emu_dropout_stream.py and tests/test_gpu_dropout_stream.py against an independent
+    Philox, tests/philox_ref.py).  The draws of elements [4q, 4q + 4) of a site's tensor -- flat channels-last index, [B][T][N][C] for a
+    block, [B][N][channels[1]] for the head -- are the four outputs of counter (q lo, q hi, position lo, position hi) under key
+    (seed lo, seed hi); an element is kept iff its draw >= floor(float32(p) * 2^32).  The position is
+
+      * eager mode: the value of ``next_offset()``, one per training forward of each module: site k (block 0, block 1, .., head) of the
+        f-th forward of a 3-site model since ``manual_seed`` sits at ``3 f + k + 1``;
+      * device-counter mode: ``module._site + CHAIN_STRIDE * chain + counter`` (``site_offset`` plus the device word), where ``chain`` is
+        the micro-batch chain of ``ops.chain_scope`` (0 outside of one; every chain numbers the elements of ITS micro-batch from 0) and
+        ``counter`` is the value of the device word when the site's kernel runs.  A step whose trainer calls ``advance()`` after it
+        (``train.train_step``, ``train.tail_step``, an unfolded ``GraphedTrainStep``) sees the counter as it stood BEFORE the step; a step
+        whose weight-pack launch carries the counter (``model._step_counters``, ``GraphedTrainStep.fold``) sees it AFTER that bump,
+        ``counter_before + SITE_STRIDE``: the pack launch is the first launch of the forward, in front of every site, and the backward
+        regenerates or reads back the same mask, so forward and backward of one step agree.  Either way the counter grows by
+        ``SITE_STRIDE`` per step, so consecutive steps -- and a tail batch between two replays -- occupy distinct positions.
+
+    ``_site`` is 1, 2, .. in construction order, below ``CHAIN_STRIDE``; chains are below ``SITE_STRIDE // CHAIN_STRIDE``: ``new_site`` /
+    ``site_offset`` raise beyond (a site past the limit would share its stream with another chain's, a chain past it with the next step's)."""
     seed: int = 0x5EED5EED
     rank_offset: int = 0      # added to every seed set through manual_seed (train.init_distributed: the data-parallel rank)
     _offset: int = 0
@@ -57,8 +76,21 @@ class DropoutStream:
 
     @classmethod
     def new_site(cls) -> int:
+        if cls._sites + 1 > cls.CHAIN_STRIDE - 1:
+            raise RuntimeError(f"DropoutStream.new_site: this process has handed out {cls._sites} dropout sites, the limit is CHAIN_STRIDE - 1 = "
+                               f"{cls.CHAIN_STRIDE - 1}: site {cls._sites + 1} would share its stream with a site of micro-batch chain 1 "
+                               f"(set DropoutStream._sites = 0 once the models built so far are gone)")
         cls._sites += 1
         return cls._sites
+
+    @classmethod
+    def site_offset(cls, site: int, chain: int) -> int:
+        """Static part of a site's position in device-counter mode: ``site + CHAIN_STRIDE * chain``."""
+        limit = cls.SITE_STRIDE // cls.CHAIN_STRIDE - 1
+        if not 0 <= chain <= limit:
+            raise RuntimeError(f"DropoutStream.site_offset: micro-batch chain {chain} is outside [0, SITE_STRIDE / CHAIN_STRIDE - 1 = {limit}]: "
+                               f"its dropout sites would share their streams with the next step's")
+        return site + cls.CHAIN_STRIDE * chain
 
     @classmethod
     def use_device_counter(cls, device):
@@ -232,7 +264,7 @@ class STConvBlock(nn.Module):
         training = self.training and self.cfg.droprate > 0.0
         counter = DropoutStream.counter if training else None
         if counter is not None:
-            offset = self._site + DropoutStream.CHAIN_STRIDE * ops.current_chain()   # static per block and chain; the device counter supplies the step
+            offset = DropoutStream.site_offset(self._site, ops.current_chain())   # static per block and chain; the device counter supplies the step
         else:
             offset = DropoutStream.next_offset() if training else 0
         self._last_call = (int(x.shape[0]), int(x.shape[2]), x.dtype)      # (what chain_status needs to find the control words again)
@@ -275,7 +307,7 @@ class OutputBlock(nn.Module):
         training = self.training and self.cfg.droprate > 0.0
         counter = DropoutStream.counter if training else None
         if counter is not None:
-            offset = self._site + DropoutStream.CHAIN_STRIDE * ops.current_chain()
+            offset = DropoutStream.site_offset(self._site, ops.current_chain())
         else:
             offset = DropoutStream.next_offset() if training else 0
         self._last_call = (int(x.shape[0]), int(x.shape[2]), x.dtype)

@@ -307,9 +307,15 @@ def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0):
     # weight-pack launch (``model._step_counters``): this eager step must not let that launch advance the WINDOW index (the tail batch
     # is handed over explicitly; the next replay has to start at the window the index already points to), so the counters are suspended
     # around the forward and the two that a tail step does consume -- dropout position and optimizer step count -- are advanced below.
+    # The dropout position: a folded step's sites see the counter AFTER the pack launch's bump, so between two replays the word still holds
+    # the position the LAST replay drew at -- this step has to move it on BEFORE its forward (as the suspended pack launch would have), or
+    # the tail batch repeats that replay's masks.  Unfolded steps leave the word at the next free position and advance it after the step.
     folded = getattr(model, "_step_counters", None)
+    drop_folded = folded is not None and any(c[0] is DropoutStream.counter for c in folded)
     if folded is not None:
         model._step_counters = None
+    if drop_folded:
+        DropoutStream.advance()
     try:
         if hi > lo:
             pred = model(x[lo:hi]).reshape(hi - lo, -1)
@@ -331,7 +337,8 @@ def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0):
     if getattr(optimizer, "trainer_owns_step", False) and hasattr(optimizer, "device_step_counter"):
         optimizer.device_step_counter(dev).add_(1)       # (the suspended pack launch would have counted this step)
     optimizer.step()
-    DropoutStream.advance()      # device-counter mode: the tail batch and the next replay must not share dropout masks
+    if not drop_folded:
+        DropoutStream.advance()  # device-counter mode: the tail batch and the next replay must not share dropout masks
     return loss_sum[0].detach()
 
 

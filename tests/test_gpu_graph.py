@@ -31,8 +31,9 @@ def test_graph_replay_equals_eager_and_masks_change():
     xs = torch.randn(6, 8, 1, 12, 207, generator=g).to(DEV)
     ys = torch.randn(6, 8, 207, generator=g).to(DEV)
 
-    # graph path (output-block nn.Dropout uses torch's own graph-safe Philox; compare ST-block behaviour with p_out = 0:
-    # a model-wide droprate applies to both, so use eval-free comparison on droprate 0 for exactness, 0.5 for mask checks)
+    # graph path (the captured step draws every mask, the head's included (fc_fwd_kernel / head_fwd_kernel), at site + device counter,
+    # the eager twin at consecutive host offsets: different positions, so the two are compared at droprate 0 for exactness and the
+    # masks are checked at 0.5; tests/test_gpu_dropout_stream.py pins the positions themselves)
     DropoutStream.use_device_counter(torch.device(DEV))
     DropoutStream.manual_seed(3)
     m1 = _make(0.0)
