@@ -30,9 +30,9 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9).  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9; the loss kinds: stgcn_head_loss.kind / .delta, stgcn_loss_grad: 10).  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
-#define STGCN_ABI_VERSION 9
+#define STGCN_ABI_VERSION 10
 
 #define STGCN_OK 0
 #define STGCN_ERR_UNSUPPORTED 1 /* shape outside what the kernels cover (message says which) */
@@ -333,12 +333,25 @@ typedef struct stgcn_outblock_params {
 } stgcn_outblock_params;
 typedef struct stgcn_outblock_grads {
     float *tc_w, *tc_b, *tc_aw, *tc_ab, *ln_w, *ln_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
-    float* loss;    /* stgcn_outblock_backward_loss only (else NULL): the MSE value, written by the gradient reduction of the call (or by
+    float* loss;    /* stgcn_outblock_backward_loss only (else NULL): the loss value, written by the gradient reduction of the call (or by
                        stgcn_grad_flush when the reduction is deferred)                                                                  */
 } stgcn_outblock_grads;
 
-/* nn.MSELoss()(pred, target) fused into the head's backward (main.py:136/167-168): the seed gradient d loss / d pred =
- * 2 (pred - target) / n * grad_scale is formed inside the fc backward kernel instead of being read, and the loss value comes out of the
+/* Loss kinds: torch.nn.MSELoss(), L1Loss() and HuberLoss(delta), each with reduction="mean" over the n predictions.  With d = pred - target:
+ *     kind               term (loss = sum of terms / n)                          d loss / d pred
+ *     STGCN_LOSS_MSE     d^2                                                     2 d grad_scale / n
+ *     STGCN_LOSS_MAE     |d|                                                     sgn(d) grad_scale / n
+ *     STGCN_LOSS_HUBER   0.5 d^2 if |d| < delta, else delta (|d| - 0.5 delta)    d grad_scale / n if |d| < delta, else delta sgn(d) grad_scale / n
+ * sgn(+-0) = 0, as torch's L1 backward gives.  One deliberate difference from torch: a NaN difference gives a NaN gradient element in EVERY
+ * kind (torch's L1 backward turns it into 0; its Huber backward keeps it).  Predictions go NaN when an in-launch wait gives up
+ * (stgcn_*_chain_status), and that NaN stays visible in the gradients as well as in the loss value.  grad_scale scales the gradient only,
+ * never the reported loss.  delta is read by STGCN_LOSS_HUBER alone and must then be finite and positive.                               */
+#define STGCN_LOSS_MSE 0
+#define STGCN_LOSS_MAE 1
+#define STGCN_LOSS_HUBER 2
+
+/* The loss of (pred, target) fused into the head's backward (nn.MSELoss(), main.py:136/167-168, or another kind): the seed gradient
+ * d loss / d pred (MSE: 2 (pred - target) / n * grad_scale) is formed inside the fc backward kernel instead of being read, and the loss value comes out of the
  * call's gradient reduction -- no separate loss launch.  pred = the (B, T1, N) output the forward of the same call chain wrote
  * (n = B*T1*N values, end_channel = 1); target: n floats, read at target + *target_index_dev * target_index_stride when an index is
  * given (device-side windowing, as in stgcn_mse_loss_grad).  With target_window_dev (nullable, needs target_index_dev; the table of
@@ -351,7 +364,8 @@ typedef struct stgcn_head_loss {
     int64_t target_index_stride;
     const int64_t* target_window_dev;  /* nullable */
     float grad_scale;                  /* e.g. 1 / world, or the tail-batch weight */
-    int32_t reserved;
+    int32_t kind;                      /* STGCN_LOSS_*; 0 = MSE (the word was `reserved`, zero, before ABI revision 10) */
+    float delta;                       /* STGCN_LOSS_HUBER only */
 } stgcn_head_loss;
 
 typedef struct stgcn_outblock_plan {
@@ -506,6 +520,13 @@ int stgcn_mse_loss_grad(const float* pred, const float* target, int64_t n, float
 int stgcn_mse_loss_grad_windows(const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
                                 const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
                                 int64_t window_floats, void* stream);
+/*      Any loss kind (STGCN_LOSS_*, the table at stgcn_head_loss), the same launch: loss[0] = sum of terms / n, dpred = d loss / d pred.
+ *      The label arguments are those of the two entries above (target_window_dev == NULL: no table, window_floats unread), and those two
+ *      are this entry with STGCN_LOSS_MSE.  STGCN_ERR_INVALID before any launch for an unknown kind or a Huber delta that is not finite
+ *      and positive.                                                                                                      */
+int stgcn_loss_grad(int32_t kind, float delta, const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
+                    float* dpred, const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
+                    int64_t window_floats, void* stream);
 
 /* ---- Evaluation: the sums behind script/utility.py:90-101 (evaluate_model: MSE in z-scored units) and :103-121 (evaluate_metric: MAE,
  *      RMSE, WMAPE after the scaler's inverse transform), formed on the device, one launch per minibatch, into a caller-owned state of

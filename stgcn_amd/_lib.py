@@ -15,11 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libstgcn_hip.so")
 
 STGCN_OK = 0
-ABI_VERSION = 9      # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
+ABI_VERSION = 10     # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
 ACT = {"glu": 0, "gtu": 1}
 GRAPH_CONV = {"cheb_graph_conv": 0, "graph_conv": 1}
 DTYPE_F32, DTYPE_BF16 = 0, 1
-EVAL_STATE_WORDS, EVAL_POS_WORDS = 264, 4      # STGCN_EVAL_STATE_WORDS (fp64), STGCN_EVAL_POS_WORDS (int64)
+LOSS = {"mse": 0, "mae": 1, "huber": 2}      # STGCN_LOSS_*
+EVAL_STATE_WORDS, EVAL_POS_WORDS = 264, 4     # STGCN_EVAL_STATE_WORDS (fp64), STGCN_EVAL_POS_WORDS (int64)
 
 _fp = C.POINTER(C.c_float)
 
@@ -87,7 +88,7 @@ class OutblockGrads(C.Structure):      # stgcn_outblock_grads: the parameter gra
 
 class HeadLoss(C.Structure):           # stgcn_head_loss
     _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("target_index_dev", C.c_void_p), ("target_index_stride", C.c_int64),
-                ("target_window_dev", C.c_void_p), ("grad_scale", C.c_float), ("reserved", C.c_int32)]
+                ("target_window_dev", C.c_void_p), ("grad_scale", C.c_float), ("kind", C.c_int32), ("delta", C.c_float)]
 
 
 HEAD_PLAN_FIELDS = ["T1", "rows", "rows_in", "out_floats", "saved_floats", "ws_floats", "sv_U", "sv_S", "sv_mean", "sv_rstd", "sv_yln",
@@ -226,6 +227,9 @@ class _Lib:
         d.stgcn_mse_loss_grad_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                   C.c_void_p, C.c_int64, C.c_void_p]
         d.stgcn_mse_loss_grad_windows.restype = C.c_int
+        d.stgcn_loss_grad.argtypes = [C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        d.stgcn_loss_grad.restype = C.c_int
         d.stgcn_eval_arm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         d.stgcn_eval_arm.restype = C.c_int
         d.stgcn_eval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -277,4 +281,4 @@ EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn
                     "stgcn_stblock_ln_hook", "stgcn_stblock_backward_hook", "stgcn_outblock_backward_hook", "stgcn_set_tc1_bwd_wgs",
                     "stgcn_set_slab_gc_precision", "stgcn_outblock_backward_loss", "stgcn_set_bwd_precision", "stgcn_set_gemm_big_nt",
                     "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush",
-                    "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate"]
+                    "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate", "stgcn_loss_grad"]

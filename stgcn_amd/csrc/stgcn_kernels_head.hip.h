@@ -138,11 +138,12 @@ struct FcBwdArgs {
     const float* W1d;     // packed PK_LIN_BWD: K = c1, cols = c0
     float* dh1;           // [rows][c1]
     float* dyln;          // [rows][c0]
-    float* part;          // [wgs][c1 + 2]: dw2 | db2 | sum (pred - target)^2 / n
+    float* part;          // [wgs][c1 + 2]: dw2 | db2 | sum of the loss terms / n
     long rows;
     int c0, c1, KCH;      // KCH = c1 / 16
     float grad_scale;     // keep_scale when dropout was active, else 1
-    // fused MSE loss (pred != null): dout[R] = 2 (pred[R] - target[R]) / n * loss_scale is formed here instead of read from `dout`
+    // fused loss (pred != null): dout[R] = d loss / d pred[R] * loss_scale (loss_term: 2 (pred[R] - target[R]) / n for MSE) is formed here
+    // instead of read from `dout`
     const float* pred;
     const float* target;
     const long* target_index;   // nullable: target += *target_index * target_index_stride
@@ -152,6 +153,8 @@ struct FcBwdArgs {
     const long* target_window;
     unsigned target_window_elems;
     float loss_scale;
+    int loss_kind;        // kLossMse / kLossMae / kLossHuber (checked on the host)
+    float loss_delta;     // Huber's switch point (> 0, finite)
     LnRowstatOut rs;      // row partials of the head's LayerNorm backward (dyln is its output gradient); rs.rowstat == null: off
 };
 
@@ -162,6 +165,38 @@ __device__ __forceinline__ const float* label_ptr(const float* y, const long* ta
     if (!tab) return y + e;
     const unsigned eu = (unsigned)e, b = eu / per_w;   // (n < 2^31: checked on the host)
     return y + tab[b] * stride + (eu - b * per_w);
+}
+
+// ---- The loss kinds (STGCN_LOSS_*): nn.MSELoss(), nn.L1Loss(), nn.HuberLoss(delta), each a mean over the n predictions ----------------
+//     kind    term of d = pred - target                                   d term / d d
+//     MSE     d^2                                                         2 d
+//     MAE     |d|                                                         sgn(d)
+//     Huber   0.5 d^2 if |d| < delta, else delta (|d| - 0.5 delta)        d if |d| < delta, else delta sgn(d)
+// sgn(+-0) = 0 as in torch; a NaN difference gives a NaN derivative in EVERY kind (torch's L1 backward turns it into 0): predictions go NaN
+// when an in-launch wait gives up, and that has to show in the gradients as well as in the loss value -- `d > 0 ? 1 : d < 0 ? -1 : d`.
+// loss_term adds the term to `sum` and returns the derivative over loss_dfactor(kind).  The sum is taken inside each kind's branch and MSE's
+// 2 is a factor of its own so that the MSE path keeps the very operations it had before there were kinds (sum += d * d as one fused
+// multiply-add; 2 * d / n * scale, resp. (2 * scale / n) * d, in that order): its results stay bit for bit.  `kind` is uniform.
+constexpr int kLossMse = 0, kLossMae = 1, kLossHuber = 2;
+
+__device__ __forceinline__ float loss_dfactor(int kind) { return kind == kLossMse ? 2.0f : 1.0f; }
+
+__device__ __forceinline__ float loss_term(int kind, float delta, float d, float& sum) {
+    if (kind == kLossMse) {
+        sum += d * d;
+        return d;
+    }
+    const float ad = fabsf(d), sg = d > 0.f ? 1.f : d < 0.f ? -1.f : d;
+    if (kind == kLossMae) {
+        sum += ad;
+        return sg;
+    }
+    if (ad < delta) {
+        sum += 0.5f * d * d;
+        return d;
+    }
+    sum += delta * (ad - 0.5f * delta);   // (NaN lands here: |NaN| < delta is false)
+    return delta * sg;
 }
 
 template <int WM, int NT, typename ET>
@@ -194,8 +229,7 @@ __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
                 float go;
                 if (a.pred) {   // uniform
                     const float df = a.pred[R] - *label_ptr(tgt, ttab, a.target_index_stride, a.target_window_elems, R);
-                    go = 2.0f * df * inv_n * a.loss_scale;
-                    if (c4 == 0) lsum += df * df;
+                    go = loss_dfactor(a.loss_kind) * loss_term(a.loss_kind, a.loss_delta, df, lsum) * inv_n * a.loss_scale;   // (lsum: only c4 == 0's is used)
                 } else {
                     go = a.dout[R];
                 }
@@ -366,26 +400,26 @@ __global__ __launch_bounds__(256) void optim_kernel(AdamwArgs a, OptimExtra x) {
 }
 
 // ================================================================================================
-// nn.MSELoss() (main.py:136, mean over all B*N elements) and its gradient in ONE launch:
+// The loss of a training step (mean over all n = B*N elements) and its gradient in ONE launch; nn.MSELoss() (main.py:136):
 //     loss = mean((pred - y)^2) ;  dpred = 2 (pred - y) * grad_scale / n
+// and likewise nn.L1Loss() / nn.HuberLoss(delta) (loss_term above).
 // The reference's loss + l.backward() head is 5 ATen launches (mse, mean, ones_like fill, mse_backward, scale) for 6624
 // elements; every launch of this path costs 5-8 us whatever its size.  One workgroup of 1024 threads, fixed summation
 // order (bitwise reproducible).
 // ================================================================================================
-__global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* pred, const float* y, long n, float gscale, float* loss,
-                                                              float* dpred, const long* y_idx_dev, long y_idx_stride, const long* y_tab,
-                                                              unsigned y_per_w) {
+__global__ __launch_bounds__(1024) void loss_grad_kernel(int kind, float delta, const float* pred, const float* y, long n, float gscale,
+                                                          float* loss, float* dpred, const long* y_idx_dev, long y_idx_stride,
+                                                          const long* y_tab, unsigned y_per_w) {
     const long* tab = nullptr;   // window table at the batch position (label_ptr)
     if (y_tab) tab = y_tab + *y_idx_dev;
     else if (y_idx_dev) y += *y_idx_dev * y_idx_stride;   // labels straight from the resident series (device-side windowing)
     extern __shared__ float stgcn_smem[];   // [16] wave sums
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float k = 2.0f * gscale / (float)n;
+    const float k = loss_dfactor(kind) * gscale / (float)n;
     float acc = 0.f;
     for (long e = tid; e < n; e += 1024) {
         const float d = pred[e] - *label_ptr(y, tab, y_idx_stride, y_per_w, e);
-        acc += d * d;
-        dpred[e] = k * d;
+        dpred[e] = k * loss_term(kind, delta, d, acc);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);

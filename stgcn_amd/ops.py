@@ -277,26 +277,42 @@ def dropout_mask(n: int, droprate: float, seed: int, offset: int, device, offset
     return out
 
 
-def mse_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``nn.MSELoss()(pred, target)`` (main.py:136/167) and d loss / d pred in one launch (stgcn_mse_loss_grad), outside
-    autograd: the trainer calls ``pred.backward(dpred)`` instead of ``loss.backward()`` (main.py:168), which removes the
-    five small ATen launches of the loss head.  Returns (loss[1], dpred like pred)."""
+LOSS_KINDS = tuple(_lib.LOSS)      # "mse", "mae", "huber": nn.MSELoss(), nn.L1Loss(), nn.HuberLoss(delta), reduction="mean"
+
+
+def loss_kind_code(kind) -> int:
+    """STGCN_LOSS_* of a loss name (an int passes through: the library refuses what it does not know)."""
+    if isinstance(kind, str):
+        if kind not in _lib.LOSS:
+            raise ValueError(f"unknown loss {kind!r}: one of {', '.join(LOSS_KINDS)} expected")
+        return _lib.LOSS[kind]
+    return int(kind)
+
+
+def loss_and_grad(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: float = 1.0,
+                  grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The loss of ``kind`` ("mse": ``nn.MSELoss()``, main.py:136/167; "mae": ``nn.L1Loss()``; "huber": ``nn.HuberLoss(delta)``) and
+    d loss / d pred in one launch (stgcn_loss_grad), outside autograd: the trainer calls ``pred.backward(dpred)`` instead of
+    ``loss.backward()`` (main.py:168), which removes the five small ATen launches of the loss head.  Unlike torch's L1 backward a NaN
+    difference gives a NaN gradient element in every kind.  Returns (loss[1], dpred like pred)."""
     L = _lib.lib()
+    code = loss_kind_code(kind)
     p = pred.detach()
     _check_device(p, "pred")
     if p.shape != target.shape or not p.is_contiguous() or not target.is_contiguous() or target.dtype != torch.float32:
-        raise ValueError(f"mse_loss_and_grad: contiguous float32 tensors of one shape expected, got {tuple(p.shape)} / {tuple(target.shape)}")
+        raise ValueError(f"loss_and_grad: contiguous float32 tensors of one shape expected, got {tuple(p.shape)} / {tuple(target.shape)}")
     loss = torch.empty(1, dtype=torch.float32, device=p.device)
     dpred = torch.empty_like(p)
-    ti, tis, tw = _index_of(target)
-    if tw is not None:      # window table: one window = one row of the leading dimension
-        L.check(L.dll.stgcn_mse_loss_grad_windows(p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(),
-                                                  dpred.data_ptr(), ti, tis, tw, p.numel() // p.shape[0], _stream_of(p)),
-                "stgcn_mse_loss_grad_windows")
-        return loss, dpred
-    L.check(L.dll.stgcn_mse_loss_grad(p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(), dpred.data_ptr(),
-                                      ti, tis, _stream_of(p)), "stgcn_mse_loss_grad")
+    ti, tis, tw = _index_of(target)      # (tw, the window table: one window = one row of the leading dimension)
+    L.check(L.dll.stgcn_loss_grad(code, float(delta), p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(),
+                                  dpred.data_ptr(), ti, tis, tw, 0 if tw is None else p.numel() // p.shape[0], _stream_of(p)),
+            "stgcn_loss_grad")
     return loss, dpred
+
+
+def mse_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``loss_and_grad`` for ``nn.MSELoss()``."""
+    return loss_and_grad(pred, target, "mse", grad_scale=grad_scale)
 
 
 EVAL_STATE_WORDS, EVAL_POS_WORDS = _lib.EVAL_STATE_WORDS, _lib.EVAL_POS_WORDS
@@ -354,9 +370,9 @@ def eval_metrics(words) -> dict:
 
 
 class _PendingLoss:
-    """MSE loss waiting to be formed inside the head's backward (``stgcn_outblock_backward_loss``): ``mse_backward`` posts it, the
+    """Loss waiting to be formed inside the head's backward (``stgcn_outblock_backward_loss``): ``loss_backward`` posts it, the
     ``_OutBlockFn.backward`` that receives the placeholder gradient takes it."""
-    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "window", "grad_scale", "loss")
+    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "window", "grad_scale", "loss", "kind", "delta")
 
 
 _pending_loss: Optional[_PendingLoss] = None
@@ -374,32 +390,39 @@ def _head_node_of(pred: torch.Tensor):
     return fn if fn is not None and type(fn).__name__ == "_OutBlockFnBackward" else None
 
 
-def mse_backward(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
-    """``l = nn.MSELoss()(pred, target); l.backward()`` (main.py:167-168) for a prediction that comes straight out of the fused output
-    head: the seed gradient is formed inside the head's fc backward kernel and the loss value comes out of the step's gradient reduction
-    (no loss launch at all).  Any other ``pred`` takes the one-launch loss kernel (``mse_loss_and_grad``) followed by
-    ``pred.backward(dpred)``.  Returns the loss (shape [1]); with an active gradient sink it is valid after the sink's flush."""
+def loss_backward(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: float = 1.0, grad_scale: float = 1.0) -> torch.Tensor:
+    """``l = nn.MSELoss()(pred, target); l.backward()`` (main.py:167-168; ``kind``: as in ``loss_and_grad``) for a prediction that comes
+    straight out of the fused output head: the seed gradient is formed inside the head's fc backward kernel and the loss value comes out of
+    the step's gradient reduction (no loss launch at all).  Any other ``pred`` takes the one-launch loss kernel (``loss_and_grad``) followed
+    by ``pred.backward(dpred)``.  Returns the loss (shape [1]); with an active gradient sink it is valid after the sink's flush."""
     global _pending_loss
+    code = loss_kind_code(kind)
     p = pred.detach()
     if (_head_node_of(pred) is None or not p.is_contiguous() or p.shape != target.shape or not target.is_contiguous()
             or target.dtype != torch.float32 or os.environ.get("STGCN_FUSED_LOSS", "1") == "0"):
-        loss, dpred = mse_loss_and_grad(pred, target, grad_scale)
+        loss, dpred = loss_and_grad(pred, target, code, delta, grad_scale)
         pred.backward(dpred)
         return loss
     _check_device(p, "pred")
     pl = _PendingLoss()
     pl.placeholder = torch.empty_like(p)            # never written, never read: its address identifies the request
     pl.pred, pl.target, pl.grad_scale = p, target, float(grad_scale)
+    pl.kind, pl.delta = code, float(delta)
     pl.index, pl.index_stride, pl.window = _index_of(target)
     pl.loss = torch.empty(1, dtype=torch.float32, device=p.device)
     _pending_loss = pl
     try:
         pred.backward(pl.placeholder)
         if _pending_loss is not None:
-            raise RuntimeError("mse_backward: the output head did not take the fused loss (was its backward run through another path?)")
+            raise RuntimeError("loss_backward: the output head did not take the fused loss (was its backward run through another path?)")
     finally:
         _pending_loss = None
     return pl.loss
+
+
+def mse_backward(pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
+    """``loss_backward`` for ``nn.MSELoss()``."""
+    return loss_backward(pred, target, "mse", grad_scale=grad_scale)
 
 
 class GradSink:
@@ -874,6 +897,7 @@ class _OutBlockFn(torch.autograd.Function):
             hl.pred, hl.target = fused_loss.pred.data_ptr(), fused_loss.target.data_ptr()
             hl.target_index_dev, hl.target_index_stride, hl.grad_scale = fused_loss.index, fused_loss.index_stride, fused_loss.grad_scale
             hl.target_window_dev = fused_loss.window
+            hl.kind, hl.delta = fused_loss.kind, fused_loss.delta
             ctx.keep_loss = fused_loss                  # the buffers outlive a deferred reduction
             L.check(L.dll.stgcn_outblock_backward_loss(C.byref(desc), C.byref(pst), x_cl.data_ptr(), C.byref(hl), saved.data_ptr(),
                                                        ctx.ws.data_ptr(), C.byref(gst), None if dx is None else dx.data_ptr(),

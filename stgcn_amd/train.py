@@ -192,12 +192,25 @@ def make_optimizer(model: torch.nn.Module, lr: float = 1e-3, weight_decay: float
     raise ValueError(f"ERROR: The {name} optimizer is undefined.")   # main.py:154
 
 
-def fwd_loss_bwd(model, x, y):
-    """forward -> MSELoss -> backward (main.py:166-168) with the loss formed inside the fused head's backward (``ops.mse_backward``;
+LOSSES = ("mse", "mae", "huber")      # nn.MSELoss() (main.py:136), nn.L1Loss(), nn.HuberLoss(huber_delta): ops.LOSS_KINDS
+
+
+def check_loss(loss: str, huber_delta: float = 1.0) -> None:
+    """Refuse a loss name the trainers do not know, or a Huber delta that is not finite and positive (``ValueError``)."""
+    import math
+    if loss not in LOSSES:
+        raise ValueError(f"unknown loss {loss!r}: one of {', '.join(LOSSES)} expected")
+    if loss == "huber" and not (math.isfinite(huber_delta) and huber_delta > 0):
+        raise ValueError(f"huber_delta = {huber_delta} must be finite and positive")
+
+
+def fwd_loss_bwd(model, x, y, loss: str = "mse", huber_delta: float = 1.0):
+    """forward -> loss (MSELoss: main.py:166-168) -> backward with the loss formed inside the fused head's backward (``ops.loss_backward``;
     one loss launch + ``pred.backward(dpred)`` for a model without the fused head).  Returns the loss (shape [])."""
     from . import ops
+    check_loss(loss, huber_delta)
     y_pred = model(x).reshape(len(x), -1)
-    return ops.mse_backward(y_pred, y)[0]
+    return ops.loss_backward(y_pred, y, loss, huber_delta)[0]
 
 
 def check_in_launch_waits(model) -> None:
@@ -253,19 +266,21 @@ class GradArena:
             p.grad = g
 
 
-def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, all_reduce=None):
-    """The loop body of main.py:165-169 with the step tail fused: forward -> backward with the MSE loss formed inside the head and
+def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, all_reduce=None, loss: str = "mse",
+                     huber_delta: float = 1.0):
+    """The loop body of main.py:165-169 with the step tail fused: forward -> backward with the loss (``loss``) formed inside the head and
     deferred reductions -> ONE launch for all gradient reductions + AdamW (world == 1), or reductions into the flat arena ->
     ``all_reduce(arena.flat)`` -> AdamW (world > 1; the 1/world of the gradient mean rides on the loss gradient).
     ``param.grad`` are the arena views (overwritten every step, never accumulated)."""
     from . import ops
+    check_loss(loss, huber_delta)
     if not fused_tail_supported(model, arena.params):
         raise RuntimeError("fused_train_step: the model has live parameters outside the fused operators (see fused_tail_supported); "
                            "use train_step")
     arena.install()
     with ops.grad_sink_scope(arena.sink):
         y_pred = model(x).reshape(len(x), -1)
-        loss = ops.mse_backward(y_pred, y, grad_scale=1.0 / world)      # (valid after the flush below)
+        value = ops.loss_backward(y_pred, y, loss, huber_delta, grad_scale=1.0 / world)      # (valid after the flush below)
     if world <= 1 and hasattr(optimizer, "flush_with"):
         optimizer.flush_with(arena.sink, arena.grads)
     else:
@@ -273,30 +288,32 @@ def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, a
         if world > 1 and all_reduce is not None:
             all_reduce(arena.flat)
         optimizer.step()
-    return loss[0]
+    return value[0]
 
 
-def train_step(model, optimizer, x, y, allreduce: Optional[FlatGradAllReduce] = None):
-    """zero_grad -> forward -> MSELoss -> backward -> [all-reduce] -> optimizer.step (main.py:165-169).
+def train_step(model, optimizer, x, y, allreduce: Optional[FlatGradAllReduce] = None, loss: str = "mse", huber_delta: float = 1.0):
+    """zero_grad -> forward -> loss (MSELoss) -> backward -> [all-reduce] -> optimizer.step (main.py:165-169).
     Returns the loss tensor (no host sync: the reference's per-step .item() at main.py:170 is deferred)."""
     from .layers import DropoutStream
+    check_loss(loss, huber_delta)
     optimizer.zero_grad(set_to_none=True)
-    loss = fwd_loss_bwd(model, x, y)
+    value = fwd_loss_bwd(model, x, y, loss, huber_delta)
     if allreduce is not None:
         allreduce()
     optimizer.step()
     DropoutStream.advance()      # (device-counter mode only: eager mode consumes a fresh host offset per forward)
-    return loss.detach()
+    return value.detach()
 
 
-def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0):
+def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0, loss: str = "mse", huber_delta: float = 1.0):
     """The partial last minibatch of an epoch (the reference iterates with ``DataLoader(drop_last=False)``, main.py:126-131, so its
     last step sees n < batch_size windows).  ``x`` / ``y`` are the GLOBAL tail batch (n windows, the same tensors on every rank);
     rank r takes a contiguous share of ceil(n / world) windows -- possibly none -- and weights its loss gradient by n_local / n, so
     the SUM all-reduce of the gradients is exactly the gradient of the mean loss over the n windows (``weight by local count``,
-    SURVEY.md section 8e).  Eager launches: a captured step has a fixed batch shape.  Returns the global mean loss (tensor)."""
+    SURVEY.md section 8e; every loss kind is a mean).  Eager launches: a captured step has a fixed batch shape.  Returns the global mean loss (tensor)."""
     from . import ops
     from .layers import DropoutStream
+    check_loss(loss, huber_delta)
     n = len(x)
     per = (n + world - 1) // world
     lo, hi = min(rank * per, n), min(rank * per + per, n)
@@ -319,8 +336,8 @@ def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0):
     try:
         if hi > lo:
             pred = model(x[lo:hi]).reshape(hi - lo, -1)
-            loss = ops.mse_backward(pred, y[lo:hi].contiguous(), grad_scale=(hi - lo) / n)
-            loss_sum = loss * ((hi - lo) / n)
+            value = ops.loss_backward(pred, y[lo:hi].contiguous(), loss, huber_delta, grad_scale=(hi - lo) / n)
+            loss_sum = value * ((hi - lo) / n)
     finally:
         if folded is not None:
             model._step_counters = folded
@@ -342,8 +359,8 @@ def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0):
     return loss_sum[0].detach()
 
 
-def chained_fwd_bwd(model, x, y, chains: int, streams=None):
-    """zero_grad'ed forward + MSE + backward of one minibatch as ``chains`` independent micro-batch chains.
+def chained_fwd_bwd(model, x, y, chains: int, streams=None, loss: str = "mse", huber_delta: float = 1.0):
+    """zero_grad'ed forward + loss (MSE, or ``loss``) + backward of one minibatch as ``chains`` independent micro-batch chains.
 
     Every kernel of this path is a 10-40 us launch whose workgroups walk load -> MFMA -> store together, so a single
     in-order chain leaves the memory system idle while the MFMA pipes run and vice versa.  The windows of a minibatch are
@@ -355,6 +372,9 @@ def chained_fwd_bwd(model, x, y, chains: int, streams=None):
     Sets ``p.grad`` and returns the detached mean loss."""
     from contextlib import nullcontext
     from . import ops
+    check_loss(loss, huber_delta)
+    F = torch.nn.functional
+    loss_fn = {"mse": F.mse_loss, "mae": F.l1_loss, "huber": lambda p, t: F.huber_loss(p, t, delta=huber_delta)}[loss]
     params = [p for p in model.parameters() if p.requires_grad]
     B = len(x)
     assert chains >= 1 and B % chains == 0, f"batch {B} does not split into {chains} chains"
@@ -369,9 +389,9 @@ def chained_fwd_bwd(model, x, y, chains: int, streams=None):
         with (torch.cuda.stream(s) if s is not None else nullcontext()), ops.chain_scope(c):
             xc, yc = x[c * Bc:(c + 1) * Bc], y[c * Bc:(c + 1) * Bc]
             pred = model(xc).reshape(Bc, -1)
-            loss = torch.nn.functional.mse_loss(pred, yc) * (1.0 / chains)
-            grads.append(torch.autograd.grad(loss, params, allow_unused=True))
-            losses.append(loss.detach())
+            value = loss_fn(pred, yc) * (1.0 / chains)
+            grads.append(torch.autograd.grad(value, params, allow_unused=True))
+            losses.append(value.detach())
     if use_streams:
         for c in range(1, chains):
             main.wait_stream(streams[c])              # join
@@ -443,8 +463,12 @@ class GraphedTrainStep:
 
     def __init__(self, model, optimizer, x_example: torch.Tensor, y_example: torch.Tensor, world: int = 1, warmup: int = 3,
                  chains: int = 1, fused: Optional[bool] = None, series: Optional[torch.Tensor] = None, n_his: int = 12,
-                 n_pred: int = 3, rank: int = 0, capture_collective: bool = False, shuffle: bool = False, shuffle_seed: int = 0):
-        """``series``: optional resident (time, N) float32 device tensor (already z-scored).  The step then takes its windows
+                 n_pred: int = 3, rank: int = 0, capture_collective: bool = False, shuffle: bool = False, shuffle_seed: int = 0,
+                 loss: str = "mse", huber_delta: float = 1.0):
+        """``loss`` / ``huber_delta``: the loss the step trains on ("mse", "mae", "huber": ``LOSSES``), frozen into the capture like every
+        other kernel argument.  An unknown name is refused here, not at the first step.
+
+        ``series``: optional resident (time, N) float32 device tensor (already z-scored).  The step then takes its windows
         straight from it (device-side windowing): window b of the minibatch is rows
         [s + b, s + b + n_his) of the series (read in place through a strided view, no (num, 1, n_his, N) tensor, no per-step
         input copies), its label row s + b + n_his + n_pred - 1 (script/dataloader.py:32-47), and s advances by the global
@@ -463,8 +487,10 @@ class GraphedTrainStep:
         operations (nccl = RCCL); the caller is expected to have probed that such a capture works on this machine
         (``probe_collective_capture``: a capture that hangs instead of raising would otherwise take the run with it)."""
         from .layers import DropoutStream
+        check_loss(loss, huber_delta)
         assert x_example.is_cuda, "hipGraph capture needs the MI355X path"
         self.model, self.opt, self.world = model, optimizer, world
+        self.loss_kind, self.huber_delta = loss, float(huber_delta)
         dev = x_example.device
         self.series, self.index, self._index_bump = series, None, None
         self._order: Optional[WindowOrder] = None
@@ -633,8 +659,8 @@ class GraphedTrainStep:
 
     def _fwd_bwd(self):
         if self.chains > 1:
-            return chained_fwd_bwd(self.model, self.x, self.y, self.chains, self.streams)
-        return fwd_loss_bwd(self.model, self.x, self.y)
+            return chained_fwd_bwd(self.model, self.x, self.y, self.chains, self.streams, self.loss_kind, self.huber_delta)
+        return fwd_loss_bwd(self.model, self.x, self.y, self.loss_kind, self.huber_delta)
 
     def _fused_fwd_bwd(self):
         """forward, one-launch loss + gradient (carrying the 1/world of the gradient mean), backward with deferred reductions;
@@ -643,7 +669,8 @@ class GraphedTrainStep:
         self.arena.install()
         with ops.grad_sink_scope(self.arena.sink):
             y_pred = self.model(self.x).reshape(len(self.x), -1)
-            loss = ops.mse_backward(y_pred, self.y, grad_scale=1.0 / self.world)      # (written by the gradient flush of the step)
+            loss = ops.loss_backward(y_pred, self.y, self.loss_kind, self.huber_delta,
+                                     grad_scale=1.0 / self.world)      # (written by the gradient flush of the step)
         if self.world > 1:
             self.arena.sink.flush(stream=torch.cuda.current_stream(self.x.device).cuda_stream)
         return loss[0]

@@ -14,6 +14,7 @@ One JSON line per epoch and one for the test metrics; a persistence forecast
 (y_hat = last observed value) on the same windows is printed beside them for scale.
 
   python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion] [--shuffle]
+                             [--loss mse | mae | huber] [--huber-delta 1.0]
 """
 import argparse
 import json
@@ -46,6 +47,9 @@ def main():
     ap.add_argument("--rows", type=int, default=34272)
     ap.add_argument("--opt", choices=("adamw", "nadamw", "lion"), default="adamw")     # main.py:59
     ap.add_argument("--shuffle", action="store_true", help="shuffled epochs: step.reshuffle() once per epoch")
+    ap.add_argument("--loss", choices=("mse", "mae", "huber"), default="mse",
+                    help="the loss the step trains on (nn.MSELoss / L1Loss / HuberLoss); val_loss stays the validation pass's MSE")
+    ap.add_argument("--huber-delta", type=float, default=1.0)
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
@@ -76,7 +80,8 @@ def main():
     val_pass = GraphedEvalPass(model, val, N_HIS, a.n_pred, BS)
     test_pass = GraphedEvalPass(model, test, N_HIS, a.n_pred, BS, scaler=zs)
     model.train()
-    step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred, shuffle=a.shuffle, shuffle_seed=42)
+    step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred, shuffle=a.shuffle, shuffle_seed=42,
+                            loss=a.loss, huber_delta=a.huber_delta)
     windows = series.shape[0] - N_HIS - a.n_pred + 1
     steps_per_epoch = windows // BS
     first_epoch_steps = steps_per_epoch
