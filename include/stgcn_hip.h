@@ -30,7 +30,7 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9; the loss kinds: stgcn_head_loss.kind / .delta, stgcn_loss_grad: 10).  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9; the loss kinds: stgcn_head_loss.kind / .delta, stgcn_loss_grad: 10).  Entry points that are only ADDED leave the number alone -- clipping by global norm (stgcn_grad_clip, stgcn_grad_norm, stgcn_optim_step_clip, stgcn_grad_flush_clip, the two state queries) changed no argument list and no layout: still 10; a library from before them lacks the symbols, and a binding that needs them finds that out when it looks them up.  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
 #define STGCN_ABI_VERSION 10
 
@@ -505,6 +505,45 @@ int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stg
 int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
                            const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_adamw_tensor* opt, int32_t opt_count,
                            const stgcn_optim_hyper* hyper, void* stream);
+
+/* ---- Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0, error_if_nonfinite=False)
+ *      followed by optimizer.step(), op for op:
+ *          total = sqrt(sum over every listed gradient element of g^2)      squares and sums in fp64, total rounded to fp32 once
+ *          coef  = min(1, max_norm / (total + 1e-6))                        fp32, as torch forms it; a NaN total gives a NaN coef
+ *          the optimizer sees coef * g (one fp32 multiply) for every element, also when coef == 1
+ *      The gradient buffers themselves keep the UNCLIPPED gradient (torch scales .grad in place; here only the update sees coef * g).
+ *      A non-finite gradient makes total, coef and then the parameters non-finite, as in torch; such steps are not skipped.
+ *      The clip state is caller-owned DEVICE memory of fp64 words, zeroed once before its first use:
+ *          state[0] = sum of squares (fp64)        state[1] = total, state[2] = coef: an fp32 value each, in the low 4 bytes of the word
+ *          state[3] = ticket word                  state[4..7] reserved               state[8 + g] = the sum of workgroup g of the launch
+ *      Its size comes from the queries below (>= STGCN_CLIP_HDR_WORDS): stgcn_grad_clip_words for the table form (the same table serves
+ *      stgcn_grad_norm and stgcn_optim_step_clip), stgcn_grad_flush_clip_words for the flush form, which takes the flush's own table
+ *      arguments.  Every entry returns STGCN_ERR_INVALID before it launches anything for a state that is NULL or smaller than that, and
+ *      for a max_norm that is NaN or <= 0 (+inf is allowed: coef == 1, the norm is still measured).
+ *      Each workgroup of a norm launch leaves its sum in its slot and takes a ticket; the last arriver adds the slots in a fixed order,
+ *      writes total and coef and re-arms the ticket (the scheme of stgcn_eval_accumulate: nothing waits, no floating-point atomics, two
+ *      passes over the same data leave bit-identical words).
+ *        stgcn_grad_norm        the norm of the `grad` tensors of a table (param / exp_avg* are not read and may be NULL); a table of any
+ *                               length gives ONE norm.  For steps whose gradient exists before the update: eager step(), the data-parallel
+ *                               step after the all-reduce (the norm of the mean gradient), the tail batch.
+ *        stgcn_grad_flush_clip  stgcn_grad_flush without an optimizer table (reduce only) whose launch also leaves the norm of every
+ *                               gradient element it wrote in the state: the fused step tail is this launch + stgcn_optim_step_clip.
+ *        stgcn_optim_step_clip  stgcn_optim_step with every gradient element multiplied by state[2] first; the state must hold the
+ *                               norm of this step (one of the two entries above, earlier on the same stream).                    */
+#define STGCN_CLIP_HDR_WORDS 8
+typedef struct stgcn_grad_clip {
+    double* state;        /* device memory, state_words fp64 words */
+    int64_t state_words;
+    float max_norm;       /* > 0, +inf allowed */
+} stgcn_grad_clip;
+int stgcn_grad_clip_words(const stgcn_adamw_tensor* tensors, int32_t count, int64_t* words);
+int stgcn_grad_flush_clip_words(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                                const stgcn_outblock_grads* head_grads, float* head_ws, int64_t* words);
+int stgcn_grad_norm(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_grad_clip* clip, void* stream);
+int stgcn_optim_step_clip(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, const stgcn_grad_clip* clip,
+                          void* stream);
+int stgcn_grad_flush_clip(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                          const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_grad_clip* clip, void* stream);
 
 /* ---- Loss: nn.MSELoss() as main.py:136 builds it (mean over all n = B*N elements) together with the gradient that
  *      l.backward() (main.py:168) feeds into the model output, in one launch:

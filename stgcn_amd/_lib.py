@@ -126,6 +126,14 @@ class OptimHyper(C.Structure):        # stgcn_optim_hyper
                 ("lr_dev", C.c_void_p), ("mu_product", C.c_float), ("mu_product_dev", C.c_void_p)]
 
 
+CLIP_HDR_WORDS = 8                             # STGCN_CLIP_HDR_WORDS (fp64); word 1 / 2: total / coef as fp32 in the low half
+CLIP_TOTAL, CLIP_COEF = 1, 2
+
+
+class GradClip(C.Structure):          # stgcn_grad_clip
+    _fields_ = [("state", C.c_void_p), ("state_words", C.c_int64), ("max_norm", C.c_float)]
+
+
 class StgcnError(RuntimeError):
     pass
 
@@ -221,6 +229,20 @@ class _Lib:
         d.stgcn_grad_flush_optim.argtypes = [C.c_int32, C.POINTER(FlushBlock), C.POINTER(OutblockDesc), C.POINTER(OutblockGrads), C.c_void_p,
                                              C.POINTER(AdamwTensor), C.c_int32, C.POINTER(OptimHyper), C.c_void_p]
         d.stgcn_grad_flush_optim.restype = C.c_int
+        # (added at ABI revision 10 without a bump -- no existing argument list or layout moved: a library from before them is stale all the same)
+        for f in ("stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip"):
+            if not hasattr(d, f):
+                raise StgcnError(f"{path} does not export {f} (built before gradient clipping was added): rebuild with "
+                                 f"`python -m stgcn_amd.build --force`")
+        d.stgcn_grad_clip_words.argtypes = [C.POINTER(AdamwTensor), C.c_int32, C.POINTER(C.c_int64)]
+        d.stgcn_grad_flush_clip_words.argtypes = [C.c_int32, C.POINTER(FlushBlock), C.POINTER(OutblockDesc), C.POINTER(OutblockGrads), C.c_void_p,
+                                                  C.POINTER(C.c_int64)]
+        d.stgcn_grad_norm.argtypes = [C.POINTER(AdamwTensor), C.c_int32, C.POINTER(GradClip), C.c_void_p]
+        d.stgcn_optim_step_clip.argtypes = [C.POINTER(AdamwTensor), C.c_int32, C.POINTER(OptimHyper), C.POINTER(GradClip), C.c_void_p]
+        d.stgcn_grad_flush_clip.argtypes = [C.c_int32, C.POINTER(FlushBlock), C.POINTER(OutblockDesc), C.POINTER(OutblockGrads), C.c_void_p,
+                                            C.POINTER(GradClip), C.c_void_p]
+        for f in ("stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip"):
+            getattr(d, f).restype = C.c_int
         d.stgcn_mse_loss_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p]
         d.stgcn_mse_loss_grad.restype = C.c_int
@@ -281,4 +303,5 @@ EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn
                     "stgcn_stblock_ln_hook", "stgcn_stblock_backward_hook", "stgcn_outblock_backward_hook", "stgcn_set_tc1_bwd_wgs",
                     "stgcn_set_slab_gc_precision", "stgcn_outblock_backward_loss", "stgcn_set_bwd_precision", "stgcn_set_gemm_big_nt",
                     "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush",
-                    "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate", "stgcn_loss_grad"]
+                    "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate", "stgcn_loss_grad",
+                    "stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip"]

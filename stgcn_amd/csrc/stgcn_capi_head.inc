@@ -549,8 +549,10 @@ int stgcn_outblock_backward_loss(const stgcn_outblock_desc* d, const stgcn_outbl
     return outblock_backward_impl(d, P, x, nullptr, hl, saved, ws, G, dx, dx_hook, stream);
 }
 
-int stgcn_adamw_step(const stgcn_adamw_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps,
-                     float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev, void* stream) {
+namespace {
+// clip_state: null = stgcn_adamw_step as it always was; else the clip form of the same launch (stgcn_optim_step_clip)
+int adamw_step_impl(const stgcn_adamw_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
+                    int64_t step, const int64_t* step_dev, const float* lr_dev, const double* clip_state, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "stgcn_adamw_step: bad tensor table");
     hipStream_t st = (hipStream_t)stream;
@@ -567,9 +569,45 @@ int stgcn_adamw_step(const stgcn_adamw_tensor* tensors, int32_t count, float lr,
         a.lb1 = (float)log((double)beta1); a.lb2 = (float)log((double)beta2);
         a.step_dev = reinterpret_cast<const long*>(step_dev); a.lr_dev = lr_dev;
         g_prof_tag = 0;
-        if (a.start[n] > 0) STGCN_LAUNCH("adamw", st, adamw_kernel, dim3(a.start[n]), dim3(kThreads), 0, a);
+        if (a.start[n] > 0) {
+            if (clip_state) STGCN_LAUNCH("adamw_clip", st, adamw_clip_kernel, dim3(a.start[n]), dim3(kThreads), 0, a, clip_state);
+            else STGCN_LAUNCH("adamw", st, adamw_kernel, dim3(a.start[n]), dim3(kThreads), 0, a);
+        }
     }
     return STGCN_OK;
+}
+
+// the workgroups of the norm launch over entries [off, off + n) of a table, and the fp64 words a table's norm needs
+int grad_norm_wgs(const stgcn_adamw_tensor* tensors, int off, int n) {
+    long chunks = 0;
+    for (int i = 0; i < n; ++i) chunks += cdiv(tensors[off + i].numel, kAdamwChunk);
+    return chunks < 1 ? 1 : (chunks > kClipMaxWgs ? kClipMaxWgs : (int)chunks);
+}
+int grad_clip_words_impl(const stgcn_adamw_tensor* tensors, int32_t count, const char* who, int64_t* words) {
+    if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "%s: bad tensor table", who);
+    int wgs = 1;
+    for (int off = 0; off < count; off += kAdamwMaxTensors) {
+        const int n = count - off < kAdamwMaxTensors ? count - off : kAdamwMaxTensors;
+        for (int i = 0; i < n; ++i)
+            if (tensors[off + i].numel < 0) return fail(STGCN_ERR_INVALID, "%s: negative numel in entry %d", who, off + i);
+        const int w = grad_norm_wgs(tensors, off, n);
+        wgs = w > wgs ? w : wgs;
+    }
+    *words = STGCN_CLIP_HDR_WORDS + wgs;
+    return STGCN_OK;
+}
+int check_clip(const stgcn_grad_clip* c, int64_t need, const char* who) {
+    if (!c || !c->state) return fail(STGCN_ERR_INVALID, "%s: NULL clip state", who);
+    if (!(c->max_norm > 0.f)) return fail(STGCN_ERR_INVALID, "%s: max_norm = %g must be > 0", who, (double)c->max_norm);
+    if (c->state_words < need)
+        return fail(STGCN_ERR_INVALID, "%s: a clip state of %lld words is too small, %lld needed", who, (long long)c->state_words, (long long)need);
+    return STGCN_OK;
+}
+}  // namespace
+
+int stgcn_adamw_step(const stgcn_adamw_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev, void* stream) {
+    return adamw_step_impl(tensors, count, lr, beta1, beta2, eps, weight_decay, step, step_dev, lr_dev, nullptr, stream);
 }
 
 int stgcn_grad_flush(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
@@ -589,14 +627,14 @@ int stgcn_grad_flush(int32_t n_blocks, const stgcn_flush_block* blocks, const st
     return launch_reduce_list(opt_count > 0 ? "reduce_adamw" : "reduce_all", RL, (hipStream_t)stream);
 }
 
-int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, void* stream) {
-    int rc = check_optim_hyper(hyper, "stgcn_optim_step");
-    if (rc) return rc;
+namespace {
+int optim_step_impl(const char* who, const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, const double* clip_state,
+                    void* stream) {
     if (hyper->kind == STGCN_OPT_ADAMW)
-        return stgcn_adamw_step(tensors, count, (float)hyper->lr, (float)hyper->beta1, (float)hyper->beta2, (float)hyper->eps, (float)hyper->weight_decay,
-                                hyper->step, hyper->step_dev, hyper->lr_dev, stream);
+        return adamw_step_impl(tensors, count, (float)hyper->lr, (float)hyper->beta1, (float)hyper->beta2, (float)hyper->eps, (float)hyper->weight_decay,
+                               hyper->step, hyper->step_dev, hyper->lr_dev, clip_state, stream);
     STGCN_FLUSH_PENDING_PACK();
-    if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "stgcn_optim_step: bad tensor table");
+    if (count < 0 || (count > 0 && !tensors)) return fail(STGCN_ERR_INVALID, "%s: bad tensor table", who);
     const bool lion = hyper->kind == STGCN_OPT_LION;
     hipStream_t st = (hipStream_t)stream;
     for (int off = 0; off < count; off += kAdamwMaxTensors) {
@@ -605,7 +643,7 @@ int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stg
         for (int i = 0; i < n; ++i) {
             const stgcn_adamw_tensor& t = tensors[off + i];
             if (!t.param || !t.grad || !t.exp_avg || (!lion && !t.exp_avg_sq) || t.numel < 0)
-                return fail(STGCN_ERR_INVALID, "stgcn_optim_step: NULL pointer in entry %d", off + i);
+                return fail(STGCN_ERR_INVALID, "%s: NULL pointer in entry %d", who, off + i);
             a.t[i].p = t.param; a.t[i].g = t.grad; a.t[i].m = t.exp_avg; a.t[i].v = lion ? nullptr : t.exp_avg_sq; a.t[i].n = (long)t.numel;
             a.start[i + 1] = a.start[i] + cdiv(t.numel, kAdamwChunk);
         }
@@ -620,10 +658,98 @@ int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stg
         x.mu_job = first;
         g_prof_tag = 0;
         if (a.start[n] > 0) {
-            if (lion) STGCN_LAUNCH("lion", st, optim_kernel<kOptLion>, dim3(a.start[n]), dim3(kThreads), 0, a, x);
+            if (clip_state) {
+                if (lion) STGCN_LAUNCH("lion_clip", st, optim_clip_kernel<kOptLion>, dim3(a.start[n]), dim3(kThreads), 0, a, x, clip_state);
+                else STGCN_LAUNCH("nadamw_clip", st, optim_clip_kernel<kOptNadamw>, dim3(a.start[n]), dim3(kThreads), 0, a, x, clip_state);
+            } else if (lion) STGCN_LAUNCH("lion", st, optim_kernel<kOptLion>, dim3(a.start[n]), dim3(kThreads), 0, a, x);
             else STGCN_LAUNCH("nadamw", st, optim_kernel<kOptNadamw>, dim3(a.start[n]), dim3(kThreads), 0, a, x);
         }
     }
+    return STGCN_OK;
+}
+}  // namespace
+
+int stgcn_optim_step(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, void* stream) {
+    const int rc = check_optim_hyper(hyper, "stgcn_optim_step");
+    if (rc) return rc;
+    return optim_step_impl("stgcn_optim_step", tensors, count, hyper, nullptr, stream);
+}
+
+int stgcn_grad_clip_words(const stgcn_adamw_tensor* tensors, int32_t count, int64_t* words) {
+    if (!words) return fail(STGCN_ERR_INVALID, "stgcn_grad_clip_words: words is NULL");
+    return grad_clip_words_impl(tensors, count, "stgcn_grad_clip_words", words);
+}
+
+int stgcn_grad_norm(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_grad_clip* clip, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    int64_t need = 0;
+    int rc = grad_clip_words_impl(tensors, count, "stgcn_grad_norm", &need);
+    if (rc) return rc;
+    rc = check_clip(clip, need, "stgcn_grad_norm");
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i)
+        if (!tensors[i].grad && tensors[i].numel > 0) return fail(STGCN_ERR_INVALID, "stgcn_grad_norm: NULL gradient in entry %d", i);
+    hipStream_t st = (hipStream_t)stream;
+    // a table longer than one launch's argument block: every launch adds its sum to state[0], the last one forms total and coef (ONE norm)
+    const int launches = count > 0 ? cdiv(count, kAdamwMaxTensors) : 1;
+    for (int l = 0; l < launches; ++l) {
+        const int off = l * kAdamwMaxTensors;
+        AdamwArgs a = zeroed<AdamwArgs>();
+        const int n = count - off < kAdamwMaxTensors ? count - off : kAdamwMaxTensors;
+        for (int i = 0; i < n; ++i) {
+            a.t[i].g = tensors[off + i].grad; a.t[i].n = (long)tensors[off + i].numel;
+            a.start[i + 1] = a.start[i] + cdiv(tensors[off + i].numel, kAdamwChunk);
+        }
+        a.count = n;
+        ClipArgs c;
+        c.state = clip->state; c.max_norm = clip->max_norm; c.first = l == 0; c.last = l == launches - 1;
+        g_prof_tag = 0;
+        STGCN_LAUNCH("grad_norm", st, grad_norm_kernel, dim3(grad_norm_wgs(tensors, off, n)), dim3(kThreads), (kThreads / 64) * sizeof(double), a, c);
+    }
+    return STGCN_OK;
+}
+
+int stgcn_optim_step_clip(const stgcn_adamw_tensor* tensors, int32_t count, const stgcn_optim_hyper* hyper, const stgcn_grad_clip* clip,
+                          void* stream) {
+    int rc = check_optim_hyper(hyper, "stgcn_optim_step_clip");
+    if (rc) return rc;
+    int64_t need = 0;
+    rc = grad_clip_words_impl(tensors, count, "stgcn_optim_step_clip", &need);
+    if (rc) return rc;
+    rc = check_clip(clip, need, "stgcn_optim_step_clip");
+    if (rc) return rc;
+    return optim_step_impl("stgcn_optim_step_clip", tensors, count, hyper, clip->state, stream);
+}
+
+int stgcn_grad_flush_clip_words(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                                const stgcn_outblock_grads* head_grads, float* head_ws, int64_t* words) {
+    if (!words) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_clip_words: words is NULL");
+    ReduceList RL;
+    const int rc = flush_job_list(RL, "stgcn_grad_flush_clip_words", n_blocks, blocks, head_desc, head_grads, head_ws, nullptr, 0, false);
+    if (rc) return rc;
+    *words = STGCN_CLIP_HDR_WORDS + (RL.ra.start[RL.nj] > 1 ? RL.ra.start[RL.nj] : 1);
+    return STGCN_OK;
+}
+
+int stgcn_grad_flush_clip(int32_t n_blocks, const stgcn_flush_block* blocks, const stgcn_outblock_desc* head_desc,
+                          const stgcn_outblock_grads* head_grads, float* head_ws, const stgcn_grad_clip* clip, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    ReduceList RL;
+    int rc = flush_job_list(RL, "stgcn_grad_flush_clip", n_blocks, blocks, head_desc, head_grads, head_ws, nullptr, 0, false);
+    if (rc) return rc;
+    if (RL.overflow) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_clip: more than %d reduction jobs in one launch", kMaxReduceJobs);
+    if (RL.nj == 0 || RL.ra.start[RL.nj] < 1) return fail(STGCN_ERR_INVALID, "stgcn_grad_flush_clip: nothing to flush");
+    rc = check_clip(clip, STGCN_CLIP_HDR_WORDS + (int64_t)RL.ra.start[RL.nj], "stgcn_grad_flush_clip");
+    if (rc) return rc;
+    RL.ra.njobs = RL.nj;
+    ReduceClipArgs a = zeroed<ReduceClipArgs>();
+    static_cast<ReduceArgs&>(a) = RL.ra;
+    a.c.state = clip->state; a.c.max_norm = clip->max_norm; a.c.first = 1; a.c.last = 1;
+    a.skip_job = -1;      // the loss value of the fused head rides in the flush as a job of its own: no gradient, not in the norm
+    for (int k = 0; k < RL.nj; ++k)
+        if (head_desc && head_grads->loss && RL.ra.job[k].dst == head_grads->loss) a.skip_job = k;
+    g_prof_tag = 0;
+    STGCN_LAUNCH("reduce_norm", (hipStream_t)stream, reduce_kernel<kOptNorm>, dim3(RL.ra.start[RL.nj]), dim3(kThreads), kThreads * 4 * sizeof(float), a);
     return STGCN_OK;
 }
 

@@ -850,4 +850,64 @@ __device__ __forceinline__ f32x4 dropout_scale4(uint64_t idx4, uint64_t seed, ui
     return k;
 }
 
+// fp64 through the 32-bit shuffles, as two words
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __shfl_xor((unsigned)u, m), hi = __shfl_xor((unsigned)(u >> 32), m);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
+
+// ================================================================================================
+// Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2): the state both norm producers fill -- grad_norm_kernel
+// over a tensor table, reduce_kernel<kOptNorm> as an epilogue of the gradient flush -- and the clip forms of the update kernels read.
+// fp64 words (stgcn_hip.h, stgcn_grad_clip):
+//     [0] sum of squares      [1] total = (float)sqrt([0]), an fp32 value in the word's low half      [2] coef, likewise
+//     [3] ticket word (low half)      [4..7] spare      [8 + g] the sum of squares workgroup g of the launch formed
+// Hand-off: the last-arriver scheme of eval_acc_kernel with the accessors of the chained launches above instead of its fences.  The slot is
+// ONE agent-scope store by lane 0 of wave 0 (written through, chain_st64), drained, then the relaxed ticket add; the workgroup that draws
+// gridDim.x - 1 reads the slots with agent-scope loads (never served from its CU's L1, chain_ld64), wave 0 adding them in a fixed order
+// (lane l: slots l, l + 64, .. in index order, then the butterfly), forms total and coef and re-arms the ticket.  Only the 8-byte slot has
+// to be visible to the last arriver, not what the workgroup wrote before: an agent-scope release fence per workgroup writes back the L2,
+// and the flush has thousands of workgroups behind a megabyte of fresh gradients (measured: profiles/grad_clip_cost.md).  Nothing waits,
+// no floating-point atomics: two passes over the same data leave bit-identical words.
+// ================================================================================================
+constexpr int kClipSumsq = 0, kClipTotal = 1, kClipCoef = 2, kClipTicket = 3, kClipHdr = 8;
+struct ClipArgs {
+    double* state;
+    float max_norm;
+    int first, last;   // a table split over several launches: the first starts the sum of squares, the last forms total and coef
+};
+__device__ __forceinline__ float clip_coef(const double* state) { return *reinterpret_cast<const float*>(state + kClipCoef); }
+// all 64 lanes of wave 0 of every workgroup call, q = the lane's share of the workgroup's sum of squares
+__device__ __forceinline__ void clip_publish(const ClipArgs& c, double q, int lane) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q += shfl_xor_f64(q, m);
+    unsigned long long* const slots = reinterpret_cast<unsigned long long*>(c.state + kClipHdr);
+    unsigned* const ticket = reinterpret_cast<unsigned*>(c.state + kClipTicket);
+    unsigned drawn = 0u;
+    if (lane == 0) {
+        chain_st64(slots + blockIdx.x, __builtin_bit_cast(unsigned long long, q));
+        chain_drain_stores();   // the slot has arrived before the ticket is drawn
+        drawn = chain_add(ticket, 1u);
+    }
+    drawn = __shfl(drawn, 0);
+    if (drawn != gridDim.x - 1u) return;
+    double t = 0.0;
+    for (unsigned g = (unsigned)lane; g < gridDim.x; g += 64u) t += __builtin_bit_cast(double, chain_ld64(slots + g));
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) t += shfl_xor_f64(t, m);
+    if (lane == 0) {
+        const double ss = c.first ? t : c.state[kClipSumsq] + t;
+        c.state[kClipSumsq] = ss;
+        if (c.last) {
+#pragma clang fp contract(off)
+            const float total = (float)sqrt(ss);
+            const float q1 = c.max_norm / (total + 1e-6f);      // torch: max_norm / (total_norm + 1e-6), fp32
+            *reinterpret_cast<float*>(c.state + kClipTotal) = total;
+            *reinterpret_cast<float*>(c.state + kClipCoef) = q1 > 1.0f ? 1.0f : q1;   // clamp(max=1): a NaN stays a NaN
+        }
+        chain_st(ticket, 0u);
+    }
+}
+
 }  // namespace stgcn

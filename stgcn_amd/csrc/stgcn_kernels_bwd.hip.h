@@ -1357,7 +1357,7 @@ __global__ __launch_bounds__(256 * kWgradGroups) void wgrad_pair_kernel(TconvBwd
 // main.py:150) and Lion (script/opt.py, main.py:152) update one element with the functions below, shared by reduce_kernel<KIND> and
 // optim_kernel<KIND>; they restate torch's fp32 CPU arithmetic op by op (contraction off, fmaf exactly where ATen's vector kernels fuse:
 // add with alpha, lerp, addcmul), so that Lion's sign(c) agrees element for element with the reference's.
-enum { kOptAdamw = 0, kOptNadamw = 1, kOptLion = 2 };
+enum { kOptAdamw = 0, kOptNadamw = 1, kOptLion = 2, kOptNorm = 3 };   // kOptNorm: no optimizer, the gradient-norm epilogue (reduce_kernel)
 struct OptimExtra {
     float omb1, omb2;   // 1 - beta1, 1 - beta2 rounded from double on the host (the factors torch forms)
     float mu_k;         // NAdamW: momentum_decay * log(0.96), mu_t = beta1 (1 - 0.5 exp(t mu_k))
@@ -1436,8 +1436,14 @@ struct ReduceOptimArgs : ReduceArgs {   // the NAdamW / Lion instantiations: Ada
     OptimExtra x;
 };
 static_assert(sizeof(ReduceOptimArgs) <= 4096, "reduce_kernel arguments exceed 4 KiB");
+struct ReduceClipArgs : ReduceArgs {    // the reduce-only form with the gradient-norm epilogue (stgcn_grad_flush_clip): no job has p
+    ClipArgs c;
+    int skip_job;   // a job that is no gradient (the fused loss value of the head) and stays out of the norm; -1: none
+};
+static_assert(sizeof(ReduceClipArgs) <= 4096, "reduce_kernel arguments exceed 4 KiB");
 template <int KIND> struct ReduceArgsOf { typedef ReduceOptimArgs type; };
 template <> struct ReduceArgsOf<kOptAdamw> { typedef ReduceArgs type; };
+template <> struct ReduceArgsOf<kOptNorm> { typedef ReduceClipArgs type; };
 // host: classify the job and return its workgroup count
 // element count from which a table takes the big-table forms below (STGCN_REDUCE_BIG: the emulator tests force them on small models)
 inline long reduce_big_threshold() {
@@ -1458,6 +1464,9 @@ inline int reduce_job_setup(ReduceJob& j) {
 }
 
 // KIND: the optimizer of the fused epilogue (jobs with p != null); kOptAdamw is also the plain reduction (no job has p)
+// kOptNorm: the plain reduction, and the sl == 0 threads that hold the finished groups -- all of them lanes of wave 0, a workgroup has at
+// most 64 groups -- square them in fp64; wave 0 leaves the workgroup's sum in its slot of the clip state and takes the ticket
+// (clip_publish): the global norm and the clip coefficient are in the state when this launch ends
 template <int KIND>
 __global__ __launch_bounds__(256) void reduce_kernel(typename ReduceArgsOf<KIND>::type a) {
     extern __shared__ float stgcn_smem[];   // [slices][32] float4
@@ -1520,6 +1529,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(typename ReduceArgsOf<KIND>
     }
     st4(stgcn_smem + (sl * kReduceElems + el) * 4, acc);
     __syncthreads();
+    double q = 0.0;   // (kOptNorm only)
     if (sl == 0 && e < n) {
         f32x4 t = zero4();
         for (int k = 0; k < kReduceSlices; ++k) t += ld4(stgcn_smem + (k * kReduceElems + el) * 4);
@@ -1550,6 +1560,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(typename ReduceArgsOf<KIND>
                     j.p[o] = np_[i];
                 }
         }
+        } else if constexpr (KIND == kOptNorm) {
+            if (jb != a.skip_job)
+                for (int i = 0; i < nw; ++i) q = fma((double)t[i], (double)t[i], q);
         } else if (j.p) {   // NAdamW / Lion on the freshly reduced gradient (same element functions as optim_kernel)
             const OptimScalars s = optim_scalars<KIND>(ts, lr, a.b1, a.lb2, a.wd, a.x);
             for (int i = 0; i < nw; ++i) {
@@ -1572,6 +1585,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(typename ReduceArgsOf<KIND>
             // NAdamW under capture: element 0 of the designated job advances the running product (the other slot than every thread read)
             if (KIND == kOptNadamw && a.x.mu_dev && jb == a.x.mu_job && e == 0) a.x.mu_dev[(long)ts & 1] = s.mu_prod;
         }
+    }
+    if constexpr (KIND == kOptNorm) {
+        if (threadIdx.x < 64) clip_publish(a.c, q, (int)threadIdx.x);
     }
 }
 

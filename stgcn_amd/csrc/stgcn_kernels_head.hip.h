@@ -367,6 +367,70 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a) {
     }
 }
 
+// The clip form (stgcn_optim_step_clip): adamw_kernel with every gradient element multiplied once by the clip coefficient that
+// stgcn_grad_norm / the flush epilogue left in the clip state (clip_publish, stgcn_device.hip.h).  A kernel of its own, so that
+// adamw_kernel compiles to the instructions it always had.
+__global__ __launch_bounds__(256) void adamw_clip_kernel(AdamwArgs a, const double* clip_state) {
+    int jb = 0;
+    while (jb + 1 < a.count && (int)blockIdx.x >= a.start[jb + 1]) ++jb;
+    const AdamwTensor& T = a.t[jb];
+    const long base = ((long)blockIdx.x - a.start[jb]) * kAdamwChunk;
+    // bias corrections 1 - beta^t: -expm1f(t * log(beta)) keeps full relative accuracy for small t (a double-precision
+    // pow() here is a multi-microsecond serial latency chain in every thread of a kernel that moves only 1 MB)
+    const float t = (float)(a.step_dev ? *a.step_dev : a.step);
+    const float lr = a.lr_dev ? *a.lr_dev : a.lr;
+    const float bc1 = -expm1f(t * a.lb1);
+    const float rs2 = rsqrtf(-expm1f(t * a.lb2));
+    const float decay = 1.0f - lr * a.wd, step_size = lr / bc1;
+    const float coef = clip_coef(clip_state);
+#pragma unroll
+    for (int k = 0; k < kAdamwChunk / kThreads; ++k) {
+        const long e = base + k * kThreads + threadIdx.x;
+        if (e < T.n) {
+            const float g = coef * T.g[e];
+            const float m = a.b1 * T.m[e] + (1.0f - a.b1) * g;
+            const float v = a.b2 * T.v[e] + (1.0f - a.b2) * g * g;
+            T.m[e] = m;
+            T.v[e] = v;
+            T.p[e] = T.p[e] * decay - step_size * (m / (sqrtf(v) * rs2 + a.eps));
+        }
+    }
+}
+
+// ================================================================================================
+// The global gradient norm of a tensor table (stgcn_grad_norm): the table and the chunks of adamw_kernel (only g and n are read), walked by
+// a grid-stride loop of at most kClipMaxWgs workgroups.  Squares and sums are fp64; the order is fixed by the table alone: thread-strided
+// chunks, a butterfly over the wave, the wave sums in wave order, then the slots (clip_publish, stgcn_device.hip.h).
+// ================================================================================================
+constexpr int kClipMaxWgs = 256;
+__global__ __launch_bounds__(256) void grad_norm_kernel(AdamwArgs a, ClipArgs c) {
+    extern __shared__ float stgcn_smem[];
+    double* red = reinterpret_cast<double*>(stgcn_smem);   // [4 waves]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunks = a.start[a.count];
+    double s = 0.0;
+    int jb = 0;
+    for (int ch = (int)blockIdx.x; ch < chunks; ch += (int)gridDim.x) {
+        while (jb + 1 < a.count && ch >= a.start[jb + 1]) ++jb;
+        const AdamwTensor& T = a.t[jb];
+        const long base = ((long)ch - a.start[jb]) * kAdamwChunk;
+#pragma unroll
+        for (int k = 0; k < kAdamwChunk / kThreads; ++k) {
+            const long e = base + k * kThreads + tid;
+            if (e < T.n) {
+                const double g = (double)T.g[e];
+                s = fma(g, g, s);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += shfl_xor_f64(s, m);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (wave != 0) return;
+    clip_publish(c, lane < kThreads / 64 ? red[lane] : 0.0, lane);
+}
+
 // ================================================================================================
 // Multi-tensor NAdamW / Lion (main.py:150 / :152): adamw_kernel's table and chunking, the per-element arithmetic of
 // nadamw_element / lion_element (stgcn_kernels_bwd.hip.h, shared with the fused epilogue of reduce_kernel<KIND>).
@@ -391,6 +455,36 @@ __global__ __launch_bounds__(256) void optim_kernel(AdamwArgs a, OptimExtra x) {
                 T.v[e] = v;
             } else {
                 lion_element(T.g[e], p, m, a.b1, a.b2, s, x);
+            }
+            T.m[e] = m;
+            T.p[e] = p;
+            if (KIND == kOptNadamw && x.mu_dev && jb == x.mu_job && e == 0) x.mu_dev[(long)t & 1] = s.mu_prod;
+        }
+    }
+}
+
+// the clip form of optim_kernel<KIND> (stgcn_optim_step_clip), a kernel of its own like adamw_clip_kernel
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_clip_kernel(AdamwArgs a, OptimExtra x, const double* clip_state) {
+    int jb = 0;
+    while (jb + 1 < a.count && (int)blockIdx.x >= a.start[jb + 1]) ++jb;
+    const AdamwTensor& T = a.t[jb];
+    const long base = ((long)blockIdx.x - a.start[jb]) * kAdamwChunk;
+    const float t = (float)(a.step_dev ? *a.step_dev : a.step);
+    const OptimScalars s = optim_scalars<KIND>(t, a.lr_dev ? *a.lr_dev : a.lr, a.b1, a.lb2, a.wd, x);
+    const float coef = clip_coef(clip_state);
+#pragma unroll
+    for (int k = 0; k < kAdamwChunk / kThreads; ++k) {
+        const long e = base + k * kThreads + threadIdx.x;
+        if (e < T.n) {
+            float p = T.p[e], m = T.m[e];
+            const float g = coef * T.g[e];
+            if (KIND == kOptNadamw) {
+                float v = T.v[e];
+                nadamw_element(g, p, m, v, a.b2, a.eps, s, x);
+                T.v[e] = v;
+            } else {
+                lion_element(g, p, m, a.b1, a.b2, s, x);
             }
             T.m[e] = m;
             T.p[e] = p;
@@ -466,12 +560,6 @@ struct EvalAccArgs {
     long num;              // windows of the split (pos only)
     int B, N;
 };
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = __shfl_xor((unsigned)u, m), hi = __shfl_xor((unsigned)(u >> 32), m);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
-}
 
 __device__ __forceinline__ void eval_finish(const EvalAccArgs& a, long fv, long k) {   // one thread, after the sums of the batch are in
     a.state[4] += (double)((a.B - fv) * (long)a.N);

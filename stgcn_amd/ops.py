@@ -445,16 +445,33 @@ class GradSink:
     def grad_for(self, p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         return None if p is None else self.by_ptr.get(p.data_ptr())
 
-    def flush(self, opt_table=None, hyper: Optional[AdamwHyper | _lib.OptimHyper] = None, stream: Optional[int] = None) -> None:
-        L = _lib.lib()
+    def _tables(self):
         arr = (FlushBlock * max(len(self.blocks), 1))()
         for i, (desc, gst, ws, _) in enumerate(self.blocks):
             arr[i].desc, arr[i].grads, arr[i].ws = C.pointer(desc), C.pointer(gst), ws.data_ptr()
         hd = hg = hws = None
         if self.head is not None:
             hd, hg, hws = C.byref(self.head[0]), C.byref(self.head[1]), self.head[2].data_ptr()
+        return arr, hd, hg, hws
+
+    def clip_words(self) -> int:
+        """fp64 words the clip state of ``flush(clip=...)`` needs for the modules this step recorded (stgcn_grad_flush_clip_words)"""
+        L = _lib.lib()
+        arr, hd, hg, hws = self._tables()
+        w = C.c_int64(0)
+        L.check(L.dll.stgcn_grad_flush_clip_words(len(self.blocks), arr, hd, hg, hws, C.byref(w)), "stgcn_grad_flush_clip_words")
+        return int(w.value)
+
+    def flush(self, opt_table=None, hyper: Optional[AdamwHyper | _lib.OptimHyper] = None, stream: Optional[int] = None, clip=None) -> None:
+        """``clip`` (a ``_lib.GradClip``; no optimizer table then): the reduce-only flush whose launch also leaves the global norm of the
+        gradients it wrote and the clip coefficient in the clip state (stgcn_grad_flush_clip).  The buffers hold the unclipped gradient."""
+        L = _lib.lib()
+        arr, hd, hg, hws = self._tables()
         n_opt = 0 if opt_table is None else len(opt_table)
-        if isinstance(hyper, _lib.OptimHyper):
+        if clip is not None:
+            assert opt_table is None and hyper is None, "the clipping flush is reduce-only: the update follows as stgcn_optim_step_clip"
+            L.check(L.dll.stgcn_grad_flush_clip(len(self.blocks), arr, hd, hg, hws, C.byref(clip), stream), "stgcn_grad_flush_clip")
+        elif isinstance(hyper, _lib.OptimHyper):
             L.check(L.dll.stgcn_grad_flush_optim(len(self.blocks), arr, hd, hg, hws, opt_table, n_opt, C.byref(hyper), stream),
                     "stgcn_grad_flush_optim")
         else:

@@ -175,20 +175,24 @@ class FlatGradAllReduce:
 
 
 def make_optimizer(model: torch.nn.Module, lr: float = 1e-3, weight_decay: float = 1e-3, name: str = "adamw",
-                   capturable: bool = False):
+                   capturable: bool = False, max_grad_norm: Optional[float] = None):
     """main.py:147-154 (adamw is the default; nadamw is NAdam with decoupled decay; lion is script/opt.py's Lion).  Each is one HIP
     launch per step and rides in the fused step tail (``flush_with``).
-    ``capturable``: keep the step counters on the device so that ``step()`` can live inside a hipGraph."""
+    ``capturable``: keep the step counters on the device so that ``step()`` can live inside a hipGraph.
+    ``max_grad_norm``: clip the gradient by its global norm inside the step (``clip_grad_norm_(params, max_grad_norm)`` + ``step()``;
+    None = off).  Every trainer of this module goes through the optimizer, so it holds for all of them: the fused tail becomes flush with
+    the norm epilogue + update, every other path norm + update -- under ``world > 1`` after the all-reduce, i.e. the norm of the mean
+    gradient, as one process on the whole batch would clip.  ``.grad`` / the arena views keep the UNCLIPPED gradient (torch scales them)."""
     params = list(model.parameters())
     if name == "adamw":
         from .optim import AdamW        # one HIP kernel per step (stgcn_adamw_step)
-        return AdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
+        return AdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable, max_grad_norm=max_grad_norm)
     if name == "nadamw":
         from .optim import NAdamW       # main.py:150 (stgcn_optim_step)
-        return NAdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
+        return NAdamW(params, lr=lr, weight_decay=weight_decay, capturable=capturable, max_grad_norm=max_grad_norm)
     if name == "lion":
         from .optim import Lion         # main.py:152
-        return Lion(params, lr=lr, weight_decay=weight_decay, capturable=capturable)
+        return Lion(params, lr=lr, weight_decay=weight_decay, capturable=capturable, max_grad_norm=max_grad_norm)
     raise ValueError(f"ERROR: The {name} optimizer is undefined.")   # main.py:154
 
 

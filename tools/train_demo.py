@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--loss", choices=("mse", "mae", "huber"), default="mse",
                     help="the loss the step trains on (nn.MSELoss / L1Loss / HuberLoss); val_loss stays the validation pass's MSE")
     ap.add_argument("--huber-delta", type=float, default=1.0)
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the gradient by its global norm inside the captured step (clip_grad_norm_ + step); the log gains grad_norm / clip_coef")
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
@@ -70,7 +72,7 @@ def main():
     torch.manual_seed(42)
     model = models.STGCNChebGraphConv(args, BLOCKS, n).to(dev)
     DropoutStream.manual_seed(42)
-    opt = make_optimizer(model, lr=1e-3, weight_decay=1e-3, name=a.opt, capturable=True)
+    opt = make_optimizer(model, lr=1e-3, weight_decay=1e-3, name=a.opt, capturable=True, max_grad_norm=a.max_grad_norm)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.95)
 
     series = torch.from_numpy(train.astype(np.float32)).to(dev)
@@ -110,9 +112,12 @@ def main():
         t0 = time.perf_counter()
         val_loss = val_pass.run()["mse"]        # one synchronise per pass (script/utility.py:90-101 on the device)
         eval_s = time.perf_counter() - t0
-        print(json.dumps({"epoch": epoch + 1, "train_loss": round(float(acc.item()) / n_steps, 6), "val_loss": round(val_loss, 6),
-                          "lr": opt.param_groups[0]["lr"], "steps": n_steps, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
-                          "train_windows_per_s": round(n_steps * BS / el, 1)}), flush=True)
+        row = {"epoch": epoch + 1, "train_loss": round(float(acc.item()) / n_steps, 6), "val_loss": round(val_loss, 6),
+               "lr": opt.param_groups[0]["lr"], "steps": n_steps, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
+               "train_windows_per_s": round(n_steps * BS / el, 1)}
+        if a.max_grad_norm is not None:         # of the epoch's last step (device words of the clip state)
+            row.update(grad_norm=round(float(opt.last_grad_norm.item()), 6), clip_coef=round(float(opt.last_clip_coef.item()), 6))
+        print(json.dumps(row), flush=True)
 
     m = test_pass.run()
     mae, rmse, wmape = m["mae"], m["rmse"], m["wmape"]
