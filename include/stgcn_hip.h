@@ -350,6 +350,32 @@ typedef struct stgcn_outblock_grads {
 #define STGCN_LOSS_MAE 1
 #define STGCN_LOSS_HUBER 2
 
+/* Masked loss: train on observed labels only (a failed detector of METR-LA / PEMS-BAY / PeMSD7-M reports 0, which the z-score turns into a
+ * label several standard deviations below the mean; DCRNN, Graph WaveNet and their successors train and score with null_val = 0).
+ * `valid` holds one byte per label, 1 = observed, 0 = missing; term / dterm are the columns of the table above; n_valid is the number of
+ * observed labels among the n of the call:
+ *     loss     = sum over valid of term(pred - target) / n_valid
+ *     dpred[e] = valid[e] ? dterm(pred[e] - target[e]) * grad_scale / n_valid : +0.0
+ *   - A masked element is selected out, not multiplied out: whatever its label or prediction holds (NaN, inf) adds nothing to the loss or
+ *     to any gradient, so NaN-coded missing readings can be masked.  A NaN at an OBSERVED element stays visible, as above.
+ *   - n_valid == 0: loss 0 and an all-zero seed gradient -- no division by zero, nothing non-finite; the optimizer step still runs.
+ *   - n_valid is formed on the device inside the launch that uses it, from row_valid: row_valid[r] is the number of observed labels in
+ *     label row r, a label row being row_elems consecutive labels (row_elems = N, the nodes).  The table is built once on the host for the
+ *     whole label tensor or series; a launch adds up the counts of its own n / row_elems rows -- an integer sum, exact and independent of
+ *     order.  No extra launch, no host value: it follows target_index_dev and target_window_dev through a captured, shuffled step.
+ *   - valid is addressed exactly as target: the same index word, stride and window table.  row_valid is addressed the same way in units
+ *     of rows, so n, the stride (when an index is given) and the labels per window (when a table is given) must be multiples of
+ *     row_elems: otherwise STGCN_ERR_INVALID before any launch, as for a NULL valid / row_valid or row_elems <= 0.
+ *   - Data-parallel: each rank takes the mean over its own observed labels and the ranks are averaged (what DDP around a masked mean
+ *     gives): grad_scale = 1 / world as without a mask.
+ * With every label observed the masked entries give the unmasked entries' results bit for bit (they perform those operations).  Under a
+ * partial mask stgcn_loss_grad_masked forms each gradient element in fp64 from the fp32 inputs and rounds it once.                      */
+typedef struct stgcn_loss_mask {
+    const uint8_t* valid;        /* one byte per label, addressed as the labels are */
+    const int32_t* row_valid;    /* observed labels per label row, addressed as the labels are, in rows */
+    int32_t row_elems;           /* labels per label row (N) */
+} stgcn_loss_mask;
+
 /* The loss of (pred, target) fused into the head's backward (nn.MSELoss(), main.py:136/167-168, or another kind): the seed gradient
  * d loss / d pred (MSE: 2 (pred - target) / n * grad_scale) is formed inside the fc backward kernel instead of being read, and the loss value comes out of the
  * call's gradient reduction -- no separate loss launch.  pred = the (B, T1, N) output the forward of the same call chain wrote
@@ -413,6 +439,11 @@ int stgcn_outblock_backward_hook(const stgcn_outblock_desc* desc, const stgcn_ou
 int stgcn_outblock_backward_loss(const stgcn_outblock_desc* desc, const stgcn_outblock_params* params, const float* x,
                                  const stgcn_head_loss* loss, const float* saved, float* ws, const stgcn_outblock_grads* grads, float* dx,
                                  const stgcn_ln_hook* dx_hook, void* stream);
+
+/* stgcn_outblock_backward_loss on observed labels only (stgcn_loss_mask above): the same launches, the fc backward kernel in its masked form */
+int stgcn_outblock_backward_loss_masked(const stgcn_outblock_desc* desc, const stgcn_outblock_params* params, const float* x,
+                                        const stgcn_head_loss* loss, const stgcn_loss_mask* mask, const float* saved, float* ws,
+                                        const stgcn_outblock_grads* grads, float* dx, const stgcn_ln_hook* dx_hook, void* stream);
 
 /* ---- Whole-model weight pack: the per-call pack launches of all ST blocks and of the head in ONE launch at the start of a
  *      training / inference step (the parameters only change in optimizer.step(), main.py:169).  Every forward whose desc
@@ -567,6 +598,12 @@ int stgcn_loss_grad(int32_t kind, float delta, const float* pred, const float* t
                     float* dpred, const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
                     int64_t window_floats, void* stream);
 
+/*      stgcn_loss_grad on observed labels only (stgcn_loss_mask, at the loss table): one launch of one workgroup, the same walk and
+ *      summation order; loss[0] = sum over valid of terms / n_valid.                                                     */
+int stgcn_loss_grad_masked(int32_t kind, float delta, const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
+                           float* dpred, const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
+                           int64_t window_floats, const stgcn_loss_mask* mask, void* stream);
+
 /* ---- Evaluation: the sums behind script/utility.py:90-101 (evaluate_model: MSE in z-scored units) and :103-121 (evaluate_metric: MAE,
  *      RMSE, WMAPE after the scaler's inverse transform), formed on the device, one launch per minibatch, into a caller-owned state of
  *      STGCN_EVAL_STATE_WORDS fp64 words that a whole pass over a split shares:
@@ -590,6 +627,19 @@ int stgcn_loss_grad(int32_t kind, float delta, const float* pred, const float* t
 int stgcn_eval_arm(double* state, int64_t* pos, void* stream);
 int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
                           int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, void* stream);
+
+/*      Masked evaluation: the same sums over the OBSERVED labels of the counted windows.  valid: one byte per label (1 = observed),
+ *      addressed as target is (pos[0] * target_stride with position words, B rows of N otherwise); a masked element is selected out,
+ *      whatever it holds.  The state has STGCN_EVAL_MASKED_STATE_WORDS words; the first 8 keep their meaning, with
+ *          state[4] = OBSERVED elements counted      state[5] = sum |d| / |y scale + mean|      state[6] the ticket word
+ *          state[8 + 6 g ..] the six sums of workgroup g
+ *      so MSE, MAE, RMSE and WMAPE are the formulas above on observed labels and MAPE = state[5] / state[4] (only meaningful with a
+ *      mask: an observed raw label of 0 makes it inf).  stgcn_eval_arm serves both state sizes.  With every label observed words 0..4
+ *      are bit for bit those of stgcn_eval_accumulate.                                                                     */
+#define STGCN_EVAL_MASKED_STATE_WORDS 392
+int stgcn_eval_accumulate_masked(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                                 int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state,
+                                 const uint8_t* valid, void* stream);
 
 /* Built-in kernel timer (no reference counterpart; feeds bench.py's roofline object).  While enabled,
  * every kernel launch is bracketed by a hipEvent pair on the launch stream.  collect() synchronises on the

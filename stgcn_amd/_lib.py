@@ -21,6 +21,7 @@ GRAPH_CONV = {"cheb_graph_conv": 0, "graph_conv": 1}
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LOSS = {"mse": 0, "mae": 1, "huber": 2}      # STGCN_LOSS_*
 EVAL_STATE_WORDS, EVAL_POS_WORDS = 264, 4     # STGCN_EVAL_STATE_WORDS (fp64), STGCN_EVAL_POS_WORDS (int64)
+EVAL_MASKED_STATE_WORDS = 392                 # STGCN_EVAL_MASKED_STATE_WORDS: six sums per workgroup slab
 
 _fp = C.POINTER(C.c_float)
 
@@ -89,6 +90,10 @@ class OutblockGrads(C.Structure):      # stgcn_outblock_grads: the parameter gra
 class HeadLoss(C.Structure):           # stgcn_head_loss
     _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("target_index_dev", C.c_void_p), ("target_index_stride", C.c_int64),
                 ("target_window_dev", C.c_void_p), ("grad_scale", C.c_float), ("kind", C.c_int32), ("delta", C.c_float)]
+
+
+class LossMask(C.Structure):           # stgcn_loss_mask
+    _fields_ = [("valid", C.c_void_p), ("row_valid", C.c_void_p), ("row_elems", C.c_int32)]
 
 
 HEAD_PLAN_FIELDS = ["T1", "rows", "rows_in", "out_floats", "saved_floats", "ws_floats", "sv_U", "sv_S", "sv_mean", "sv_rstd", "sv_yln",
@@ -257,6 +262,17 @@ class _Lib:
         d.stgcn_eval_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         d.stgcn_eval_accumulate.restype = C.c_int
+        # (the masked loss and metrics: added at ABI revision 10 without a bump, like the clip entries)
+        for f in ("stgcn_loss_grad_masked", "stgcn_outblock_backward_loss_masked", "stgcn_eval_accumulate_masked"):
+            if not hasattr(d, f):
+                raise StgcnError(f"{path} does not export {f} (built before the masked loss was added): rebuild with "
+                                 f"`python -m stgcn_amd.build --force`")
+            getattr(d, f).restype = C.c_int
+        d.stgcn_loss_grad_masked.argtypes = d.stgcn_loss_grad.argtypes[:-1] + [C.POINTER(LossMask), C.c_void_p]
+        d.stgcn_outblock_backward_loss_masked.argtypes = [C.POINTER(OutblockDesc), C.POINTER(OutblockParams), C.c_void_p, C.POINTER(HeadLoss),
+                                                          C.POINTER(LossMask), C.c_void_p, C.c_void_p, C.POINTER(OutblockGrads), C.c_void_p,
+                                                          C.POINTER(LnHook), C.c_void_p]
+        d.stgcn_eval_accumulate_masked.argtypes = d.stgcn_eval_accumulate.argtypes[:-1] + [C.c_void_p, C.c_void_p]
         d.stgcn_profile_enable.argtypes = [C.c_int]
         d.stgcn_profile_enable.restype = C.c_int
         d.stgcn_profile_collect.argtypes = [C.c_char_p, C.c_size_t]
@@ -304,4 +320,5 @@ EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn
                     "stgcn_set_slab_gc_precision", "stgcn_outblock_backward_loss", "stgcn_set_bwd_precision", "stgcn_set_gemm_big_nt",
                     "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush",
                     "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate", "stgcn_loss_grad",
-                    "stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip"]
+                    "stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip",
+                    "stgcn_loss_grad_masked", "stgcn_outblock_backward_loss_masked", "stgcn_eval_accumulate_masked"]

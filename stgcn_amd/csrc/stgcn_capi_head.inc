@@ -191,9 +191,25 @@ int check_loss_kind(const char* who, int32_t kind, float delta) {
     return STGCN_OK;
 }
 
+// the mask of a masked loss entry, refused before anything is launched: n labels in whole rows of row_elems, and -- where the labels are
+// read through an index word or a window table -- a stride and a window size in whole rows, so that row_valid can be addressed like them
+int check_loss_mask(const char* who, const stgcn_loss_mask* mk, int64_t n, bool indexed, int64_t stride, bool table, int64_t window_floats) {
+    if (!mk || !mk->valid || !mk->row_valid) return fail(STGCN_ERR_INVALID, "%s: NULL mask (valid / row_valid)", who);
+    if (mk->row_elems <= 0) return fail(STGCN_ERR_INVALID, "%s: row_elems = %d must be positive", who, (int)mk->row_elems);
+    if (n % mk->row_elems != 0)
+        return fail(STGCN_ERR_INVALID, "%s: n = %lld labels are not whole rows of row_elems = %d", who, (long long)n, (int)mk->row_elems);
+    if (indexed && (stride < 0 || stride % mk->row_elems != 0))
+        return fail(STGCN_ERR_INVALID, "%s: the label stride %lld is not a multiple of row_elems = %d (row_valid is addressed in rows)", who,
+                    (long long)stride, (int)mk->row_elems);
+    if (table && window_floats % mk->row_elems != 0)
+        return fail(STGCN_ERR_INVALID, "%s: %lld labels per window are not a multiple of row_elems = %d", who, (long long)window_floats,
+                    (int)mk->row_elems);
+    return STGCN_OK;
+}
+
 int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
-                           const stgcn_head_loss* hl, const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx,
-                           const stgcn_ln_hook* dx_hook, void* stream) {
+                           const stgcn_head_loss* hl, const stgcn_loss_mask* mk, const float* saved, float* ws,
+                           const stgcn_outblock_grads* G, float* dx, const stgcn_ln_hook* dx_hook, void* stream) {
     STGCN_FLUSH_PENDING_PACK();
     stgcn_outblock_plan pl;
     int rc = stgcn_outblock_plan_query(d, &pl);
@@ -203,6 +219,11 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
     rc = check_dx_hook("stgcn_outblock_backward", dx_hook, d->N, d->c_in, d->need_dx, d->dtype);
     if (rc) return rc;
     const HeadGeom g = head_geom(d);
+    if (mk) {
+        rc = check_loss_mask("stgcn_outblock_backward_loss_masked", mk, g.rows, hl->target_index_dev != nullptr, hl->target_index_stride,
+                             hl->target_window_dev != nullptr, g.rows / d->B);
+        if (rc) return rc;
+    }
     hipStream_t st = (hipStream_t)stream;
     g_prof_tag = 0;
     g_bf16 = d->dtype == STGCN_DTYPE_BF16;
@@ -222,13 +243,20 @@ int outblock_backward_impl(const stgcn_outblock_desc* d, const stgcn_outblock_pa
             a.loss_kind = hl->kind; a.loss_delta = hl->delta;
             a.target_window = reinterpret_cast<const long*>(hl->target_window_dev); a.target_window_elems = (unsigned)(g.rows / d->B);
         }
+        if (mk) { a.valid = mk->valid; a.row_valid = mk->row_valid; a.mask_row_elems = mk->row_elems; }
         if (own_rowstats) {   // the head's LayerNorm-backward row partials in this kernel's epilogue (dyln is that LayerNorm's output gradient)
             a.rs.rowstat = reinterpret_cast<float2*>(ws + pl.ws_rowstat_b); a.rs.U = saved + pl.sv_U; a.rs.S = saved + pl.sv_S; a.rs.gamma = P->ln_w;
             a.rs.mean = saved + pl.sv_mean; a.rs.rstd = saved + pl.sv_rstd; a.rs.N = d->N; a.rs.C = d->c0; a.rs.act = d->act; a.rs.training = 0;
             a.rs.keep_scale = 1.f;
         }
         const size_t lds = (size_t)(head_fc_tile_rows() * (d->c1 + 4) + 8 * d->c1 + 16) * sizeof(float);
-        if (head_fc_tile_rows() == 16) {
+        if (mk) {   // the masked instances: the same grid, block, LDS and label
+            if (head_fc_tile_rows() == 16) {
+                if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 2, ET, true>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+                else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 1, ET, true>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+            } else if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 2, ET, true>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+            else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 1, ET, true>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
+        } else if (head_fc_tile_rows() == 16) {
             if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
             else STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<1, 1, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
         } else if (d->c0 == 128) STGCN_LAUNCH_ETB("head.fc_bwd", st, (fc_bwd_kernel<2, 2, ET>), dim3(g.fc_wgs), dim3(kThreads), lds, a);
@@ -528,25 +556,43 @@ int stgcn_outblock_chain_status(const stgcn_outblock_desc* d, const float* ws, u
 
 int stgcn_outblock_backward(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
                             const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx, void* stream) {
-    return outblock_backward_impl(d, P, x, dout, nullptr, saved, ws, G, dx, nullptr, stream);
+    return outblock_backward_impl(d, P, x, dout, nullptr, nullptr, saved, ws, G, dx, nullptr, stream);
 }
 
 int stgcn_outblock_backward_hook(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const float* dout,
                                  const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx, const stgcn_ln_hook* dx_hook,
                                  void* stream) {
-    return outblock_backward_impl(d, P, x, dout, nullptr, saved, ws, G, dx, dx_hook, stream);
+    return outblock_backward_impl(d, P, x, dout, nullptr, nullptr, saved, ws, G, dx, dx_hook, stream);
 }
+
+namespace {
+int check_head_loss(const char* who, const stgcn_head_loss* hl, const stgcn_outblock_grads* G) {
+    if (!hl || !hl->pred || !hl->target) return fail(STGCN_ERR_INVALID, "%s: NULL pred / target", who);
+    if (!G || !G->loss) return fail(STGCN_ERR_INVALID, "%s: grads->loss is NULL", who);
+    const int rc = check_loss_kind(who, hl->kind, hl->delta);
+    if (rc) return rc;
+    if (hl->target_window_dev && !hl->target_index_dev)
+        return fail(STGCN_ERR_INVALID, "%s: target_window_dev (window table) needs target_index_dev != NULL", who);
+    return STGCN_OK;
+}
+}  // namespace
 
 int stgcn_outblock_backward_loss(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x, const stgcn_head_loss* hl,
                                  const float* saved, float* ws, const stgcn_outblock_grads* G, float* dx, const stgcn_ln_hook* dx_hook,
                                  void* stream) {
-    if (!hl || !hl->pred || !hl->target) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: NULL pred / target");
-    if (!G || !G->loss) return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: grads->loss is NULL");
-    const int rc = check_loss_kind("stgcn_outblock_backward_loss", hl->kind, hl->delta);
+    const int rc = check_head_loss("stgcn_outblock_backward_loss", hl, G);
     if (rc) return rc;
-    if (hl->target_window_dev && !hl->target_index_dev)
-        return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss: target_window_dev (window table) needs target_index_dev != NULL");
-    return outblock_backward_impl(d, P, x, nullptr, hl, saved, ws, G, dx, dx_hook, stream);
+    return outblock_backward_impl(d, P, x, nullptr, hl, nullptr, saved, ws, G, dx, dx_hook, stream);
+}
+
+int stgcn_outblock_backward_loss_masked(const stgcn_outblock_desc* d, const stgcn_outblock_params* P, const float* x,
+                                        const stgcn_head_loss* hl, const stgcn_loss_mask* mask, const float* saved, float* ws,
+                                        const stgcn_outblock_grads* G, float* dx, const stgcn_ln_hook* dx_hook, void* stream) {
+    const int rc = check_head_loss("stgcn_outblock_backward_loss_masked", hl, G);
+    if (rc) return rc;
+    if (!mask || !mask->valid || !mask->row_valid || mask->row_elems <= 0)
+        return fail(STGCN_ERR_INVALID, "stgcn_outblock_backward_loss_masked: NULL mask (valid / row_valid) or row_elems <= 0");
+    return outblock_backward_impl(d, P, x, nullptr, hl, mask, saved, ws, G, dx, dx_hook, stream);
 }
 
 namespace {
@@ -783,24 +829,51 @@ int stgcn_grad_flush_optim(int32_t n_blocks, const stgcn_flush_block* blocks, co
     return launch_reduce_list_optim(lion ? "reduce_lion" : "reduce_nadamw", RL, hyper->kind, x, (hipStream_t)stream);
 }
 
+namespace {
+// the argument checks the masked and the unmasked loss launch share
+int check_loss_grad(const char* who, int32_t kind, float delta, const float* pred, const float* target, int64_t n, const float* loss,
+                    const float* dpred, const int64_t* target_index_dev, const int64_t* target_window_dev, int64_t window_floats) {
+    const int rc = check_loss_kind(who, kind, delta);
+    if (rc) return rc;
+    if (!pred || !target || !loss || !dpred || n < 1) return fail(STGCN_ERR_INVALID, "%s: NULL buffer or n < 1", who);
+    if (target_window_dev) {
+        if (!target_index_dev) return fail(STGCN_ERR_INVALID, "%s: target_window_dev (window table) needs target_index_dev != NULL", who);
+        if (window_floats < 1 || n % window_floats != 0 || n >= (1ll << 31))
+            return fail(STGCN_ERR_INVALID, "%s: n = %lld must be a multiple of window_floats = %lld and below 2^31", who, (long long)n,
+                        (long long)window_floats);
+    }
+    return STGCN_OK;
+}
+}  // namespace
+
 int stgcn_loss_grad(int32_t kind, float delta, const float* pred, const float* target, int64_t n, float grad_scale, float* loss, float* dpred,
                     const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev, int64_t window_floats,
                     void* stream) {
     STGCN_FLUSH_PENDING_PACK();
-    int rc = check_loss_kind("stgcn_loss_grad", kind, delta);
+    const int rc = check_loss_grad("stgcn_loss_grad", kind, delta, pred, target, n, loss, dpred, target_index_dev, target_window_dev, window_floats);
     if (rc) return rc;
-    if (!pred || !target || !loss || !dpred || n < 1) return fail(STGCN_ERR_INVALID, "stgcn_loss_grad: NULL buffer or n < 1");
-    if (target_window_dev) {
-        if (!target_index_dev) return fail(STGCN_ERR_INVALID, "stgcn_loss_grad: target_window_dev (window table) needs target_index_dev != NULL");
-        if (window_floats < 1 || n % window_floats != 0 || n >= (1ll << 31))
-            return fail(STGCN_ERR_INVALID, "stgcn_loss_grad: n = %lld must be a multiple of window_floats = %lld and below 2^31", (long long)n,
-                        (long long)window_floats);
-    }
     g_prof_tag = 0;
     const char* label = kind == STGCN_LOSS_MSE ? "mse_loss_grad" : "loss_grad";   // (the MSE launch keeps the label the kernel timer's readers know)
     STGCN_LAUNCH(label, (hipStream_t)stream, loss_grad_kernel, dim3(1), dim3(1024), 16 * sizeof(float), (int)kind, delta, pred, target,
                  (long)n, grad_scale, loss, dpred, reinterpret_cast<const long*>(target_index_dev), (long)target_index_stride,
                  reinterpret_cast<const long*>(target_window_dev), target_window_dev ? (unsigned)window_floats : 0u);
+    return STGCN_OK;
+}
+
+int stgcn_loss_grad_masked(int32_t kind, float delta, const float* pred, const float* target, int64_t n, float grad_scale, float* loss,
+                           float* dpred, const int64_t* target_index_dev, int64_t target_index_stride, const int64_t* target_window_dev,
+                           int64_t window_floats, const stgcn_loss_mask* mask, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    int rc = check_loss_grad("stgcn_loss_grad_masked", kind, delta, pred, target, n, loss, dpred, target_index_dev, target_window_dev, window_floats);
+    if (rc) return rc;
+    rc = check_loss_mask("stgcn_loss_grad_masked", mask, n, target_index_dev != nullptr, target_index_stride, target_window_dev != nullptr,
+                         window_floats);
+    if (rc) return rc;
+    g_prof_tag = 0;
+    STGCN_LAUNCH("loss_grad_masked", (hipStream_t)stream, loss_grad_masked_kernel, dim3(1), dim3(1024), 16 * sizeof(float), (int)kind, delta, pred,
+                 target, (long)n, grad_scale, loss, dpred, reinterpret_cast<const long*>(target_index_dev), (long)target_index_stride,
+                 reinterpret_cast<const long*>(target_window_dev), target_window_dev ? (unsigned)window_floats : 0u, mask->valid, mask->row_valid,
+                 (int)mask->row_elems);
     return STGCN_OK;
 }
 
@@ -824,19 +897,19 @@ int stgcn_eval_arm(double* state, int64_t* pos, void* stream) {
     return STGCN_OK;
 }
 
-int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
-                          int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, void* stream) {
-    STGCN_FLUSH_PENDING_PACK();
-    if (!state) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: state is NULL");
-    if (!pred || !target) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: NULL pred / target");
-    if (B < 1 || N < 1) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: n = B * N must be positive (B=%d, N=%d)", B, N);
-    if ((scale == nullptr) != (mean == nullptr)) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: scale and mean come together (both or neither)");
-    if (first_valid < 0 || first_valid >= B)
-        return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: first_valid=%lld outside [0, B=%d)", (long long)first_valid, B);
+namespace {
+// checks, kernel arguments and grid shared by the masked and the unmasked accumulate launch
+int eval_acc_setup(const char* who, const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                   int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, EvalAccArgs* out, int* wgs_out) {
+    if (!state) return fail(STGCN_ERR_INVALID, "%s: state is NULL", who);
+    if (!pred || !target) return fail(STGCN_ERR_INVALID, "%s: NULL pred / target", who);
+    if (B < 1 || N < 1) return fail(STGCN_ERR_INVALID, "%s: n = B * N must be positive (B=%d, N=%d)", who, B, N);
+    if ((scale == nullptr) != (mean == nullptr)) return fail(STGCN_ERR_INVALID, "%s: scale and mean come together (both or neither)", who);
+    if (first_valid < 0 || first_valid >= B) return fail(STGCN_ERR_INVALID, "%s: first_valid=%lld outside [0, B=%d)", who, (long long)first_valid, B);
     if (pos) {
-        if (first_valid != 0) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: with position words first_valid is read from them (pass 0)");
-        if (num_windows < B) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: %lld windows are fewer than one batch of %d", (long long)num_windows, B);
-        if (target_stride < 0) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate: negative target stride");
+        if (first_valid != 0) return fail(STGCN_ERR_INVALID, "%s: with position words first_valid is read from them (pass 0)", who);
+        if (num_windows < B) return fail(STGCN_ERR_INVALID, "%s: %lld windows are fewer than one batch of %d", who, (long long)num_windows, B);
+        if (target_stride < 0) return fail(STGCN_ERR_INVALID, "%s: negative target stride", who);
     }
     EvalAccArgs a;
     a.pred = pred; a.target = target; a.scale = scale; a.mean = mean; a.state = state;
@@ -849,8 +922,38 @@ int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int
         wgs = cdiv(n, 2 * kEvalThreads);
         wgs = wgs < 2 ? 2 : (wgs > kEvalMaxWgs ? kEvalMaxWgs : wgs);
     }
+    *out = a;
+    *wgs_out = wgs;
+    return STGCN_OK;
+}
+}  // namespace
+
+int stgcn_eval_accumulate(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                          int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    EvalAccArgs a;
+    int wgs = 1;
+    const int rc = eval_acc_setup("stgcn_eval_accumulate", pred, target, B, N, scale, mean, first_valid, pos, target_stride, num_windows, state, &a, &wgs);
+    if (rc) return rc;
     g_prof_tag = 0;
     STGCN_LAUNCH("eval_acc", (hipStream_t)stream, eval_acc_kernel, dim3(wgs), dim3(kEvalThreads), (kEvalThreads / 64) * 4 * sizeof(double), a);
+    return STGCN_OK;
+}
+
+int stgcn_eval_accumulate_masked(const float* pred, const float* target, int32_t B, int32_t N, const float* scale, const float* mean,
+                                 int64_t first_valid, int64_t* pos, int64_t target_stride, int64_t num_windows, double* state,
+                                 const uint8_t* valid, void* stream) {
+    STGCN_FLUSH_PENDING_PACK();
+    EvalAccArgs a;
+    int wgs = 1;
+    const int rc = eval_acc_setup("stgcn_eval_accumulate_masked", pred, target, B, N, scale, mean, first_valid, pos, target_stride, num_windows, state,
+                                  &a, &wgs);
+    if (rc) return rc;
+    if (!valid) return fail(STGCN_ERR_INVALID, "stgcn_eval_accumulate_masked: valid is NULL");
+    static_assert(STGCN_EVAL_MASKED_STATE_WORDS == kEvalHdr + kEvalMaxWgs * kEvalMaskedSums, "masked state size");
+    g_prof_tag = 0;
+    STGCN_LAUNCH("eval_acc_masked", (hipStream_t)stream, eval_acc_masked_kernel, dim3(wgs), dim3(kEvalThreads),
+                 (kEvalThreads / 64) * kEvalMaskedSums * sizeof(double), a, valid);
     return STGCN_OK;
 }
 

@@ -155,6 +155,11 @@ struct FcBwdArgs {
     float loss_scale;
     int loss_kind;        // kLossMse / kLossMae / kLossHuber (checked on the host)
     float loss_delta;     // Huber's switch point (> 0, finite)
+    // masked loss (fc_bwd_kernel<.., MASKED = true> only; see the masked forms below): one byte per label, addressed as `target`, and the
+    // observed labels per label row of mask_row_elems labels, addressed the same way in units of rows
+    const uint8_t* valid;
+    const int* row_valid;
+    int mask_row_elems;
     LnRowstatOut rs;      // row partials of the head's LayerNorm backward (dyln is its output gradient); rs.rowstat == null: off
 };
 
@@ -199,7 +204,38 @@ __device__ __forceinline__ float loss_term(int kind, float delta, float d, float
     return delta * sg;
 }
 
-template <int WM, int NT, typename ET>
+// ---- The masked forms (stgcn_loss_mask): train on observed labels only --------------------------------------------------------------
+//     loss = sum over valid of term / n_valid ;  dpred[e] = valid[e] ? dterm * grad_scale / n_valid : +0.0
+// A masked element is SELECTED out: its label and prediction are still loaded (finite or not), its term never reaches the sum and its
+// gradient is the constant +0.0, so NaN- or inf-coded missing readings cost nothing.  `valid` (one byte per label) is addressed exactly
+// as the labels are (label_at with the same base shift, table, stride and window size); `row_valid` (int32 observed labels per label row
+// of row_elems labels) the same way in units of rows.  n_valid is the INTEGER sum of the launch's own rows / row_elems counts, formed by
+// every workgroup for itself before it touches an element: exact, order-free, no launch and no host value -- it follows the index word
+// and the window table of a captured step.  n_valid == 0: loss 0, every gradient element +0.0.
+template <typename T>
+__device__ __forceinline__ T label_at(const T* y, const long* tab, long stride, unsigned per_w, long e) {   // label_ptr for any element type
+    if (!tab) return y[e];
+    const unsigned eu = (unsigned)e, b = eu / per_w;
+    return y[tab[b] * stride + (eu - b * per_w)];
+}
+
+// the observed labels among the launch's n_rows label rows: thread-strided integer sum, butterfly, the wave sums through `slots` (LDS,
+// one int per wave).  Every thread of the workgroup calls and gets the same value; ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ int mask_count(const int* row_valid, const long* tab, long stride_rows, unsigned rows_per_w, long n_rows, int* slots) {
+    int c = 0;
+    for (long r = threadIdx.x; r < n_rows; r += THREADS) c += label_at<int>(row_valid, tab, stride_rows, rows_per_w, r);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = c;
+    __syncthreads();
+    int n = 0;
+    for (int w = 0; w < THREADS / 64; ++w) n += slots[w];
+    return n;
+}
+
+// MASKED (the fused loss only): the masked form above.  A template parameter, so that the unmasked instances keep their instructions.
+template <int WM, int NT, typename ET, bool MASKED = false>
 __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
     constexpr int TR = WM * 16;
     extern __shared__ float stgcn_smem[];
@@ -216,7 +252,19 @@ __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
     const long* ttab = nullptr;
     if (a.pred && a.target_window) ttab = a.target_window + *a.target_index;
     else if (a.pred && a.target_index) tgt += *a.target_index * a.target_index_stride;
-    const float inv_n = 1.0f / (float)a.rows;
+    float inv_n = 1.0f / (float)a.rows;
+    const uint8_t* vld = a.valid;
+    if (MASKED) {   // 1 / n_valid from the row counts of this launch's labels (red is not written before the tile loop's first barrier)
+        const int re = a.mask_row_elems;
+        const int* rv = a.row_valid;
+        if (!ttab && a.target_index) {
+            vld += *a.target_index * a.target_index_stride;
+            rv += *a.target_index * (a.target_index_stride / re);
+        }
+        const int nv = mask_count<kThreads>(rv, ttab, a.target_index_stride / re, a.target_window_elems / (unsigned)re, a.rows / re,
+                                            reinterpret_cast<int*>(red));
+        inv_n = nv > 0 ? 1.0f / (float)nv : 0.f;
+    }
     PreW<NT, 8> w;   // fc1 weight fragments of the whole K = c1 (8 chunks), requested before the first tile is touched
     pre_load_weights<NT, 8>(w, a.W1d, a.KCH, wave, 4);
     for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -227,7 +275,14 @@ __global__ __launch_bounds__(256) void fc_bwd_kernel(FcBwdArgs a) {
             f32x4 d = zero4();
             if (R < a.rows) {
                 float go;
-                if (a.pred) {   // uniform
+                if (MASKED) {
+                    const float df = a.pred[R] - *label_ptr(tgt, ttab, a.target_index_stride, a.target_window_elems, R);
+                    const bool ok = label_at<uint8_t>(vld, ttab, a.target_index_stride, a.target_window_elems, R) != 0;
+                    float ls = lsum;   // (the term is added as the unmasked form adds it, and kept only for an observed label)
+                    const float gv = loss_dfactor(a.loss_kind) * loss_term(a.loss_kind, a.loss_delta, df, ls) * inv_n * a.loss_scale;
+                    go = ok ? gv : 0.f;
+                    lsum = ok ? ls : lsum;
+                } else if (a.pred) {   // uniform
                     const float df = a.pred[R] - *label_ptr(tgt, ttab, a.target_index_stride, a.target_window_elems, R);
                     go = loss_dfactor(a.loss_kind) * loss_term(a.loss_kind, a.loss_delta, df, lsum) * inv_n * a.loss_scale;   // (lsum: only c4 == 0's is used)
                 } else {
@@ -526,6 +581,59 @@ __global__ __launch_bounds__(1024) void loss_grad_kernel(int kind, float delta, 
     }
 }
 
+// The masked form (stgcn_loss_grad_masked; the semantics at label_at above): the same single workgroup, the same walk and summation order,
+// n_valid from the row counts first.  With every label observed (n_valid == n, uniform) it performs the operations of loss_grad_kernel on
+// the same values: that launch bit for bit.  Otherwise nothing pins the gradient to those operations, and three fp32 roundings (the
+// difference, 1 / n_valid, the product) can leave an element 1.8e-7 off: the element is formed in fp64 from the fp32 inputs and rounded
+// once (loss_dterm64; one fp64 multiply per element of a launch that is all latency).  The loss value is summed as the unmasked form sums it.
+__device__ __forceinline__ double loss_dterm64(int kind, float delta, double d) {   // d term / d d over loss_dfactor(kind), as loss_term returns it
+    if (kind == kLossMse) return d;
+    const double sg = d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : d;   // (sgn(+-0) = 0, NaN stays NaN)
+    if (kind == kLossMae) return sg;
+    return fabs(d) < (double)delta ? d : (double)delta * sg;
+}
+
+__global__ __launch_bounds__(1024) void loss_grad_masked_kernel(int kind, float delta, const float* pred, const float* y, long n, float gscale,
+                                                                 float* loss, float* dpred, const long* y_idx_dev, long y_idx_stride,
+                                                                 const long* y_tab, unsigned y_per_w, const uint8_t* valid,
+                                                                 const int* row_valid, int row_elems) {
+    const long* tab = nullptr;
+    if (y_tab) tab = y_tab + *y_idx_dev;
+    else if (y_idx_dev) {
+        y += *y_idx_dev * y_idx_stride;
+        valid += *y_idx_dev * y_idx_stride;
+        row_valid += *y_idx_dev * (y_idx_stride / row_elems);
+    }
+    extern __shared__ float stgcn_smem[];   // [16] wave sums (the row counts first, then the terms)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = mask_count<1024>(row_valid, tab, y_idx_stride / row_elems, y_per_w / (unsigned)row_elems, n / row_elems,
+                                    reinterpret_cast<int*>(stgcn_smem));
+    __syncthreads();   // the counts are read before the slots take the wave sums
+    const bool full = (long)nv == n;
+    const float k = nv > 0 ? loss_dfactor(kind) * gscale / (float)nv : 0.f;
+    const double kd = nv > 0 ? (double)loss_dfactor(kind) * (double)gscale / (double)nv : 0.0;
+    float acc = 0.f;
+    for (long e = tid; e < n; e += 1024) {
+        const float p = pred[e], t = *label_ptr(y, tab, y_idx_stride, y_per_w, e);
+        const float d = p - t;
+        const bool ok = label_at<uint8_t>(valid, tab, y_idx_stride, y_per_w, e) != 0;
+        float s = acc;
+        float g = k * loss_term(kind, delta, d, s);
+        if (!full) g = (float)(kd * loss_dterm64(kind, delta, (double)p - (double)t));
+        dpred[e] = ok ? g : 0.f;
+        acc = ok ? s : acc;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    if (lane == 0) stgcn_smem[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int w = 0; w < 16; ++w) s += stgcn_smem[w];
+        loss[0] = nv > 0 ? s / (float)nv : 0.f;
+    }
+}
+
 // ================================================================================================
 // Evaluation metrics of one minibatch, added into a device-resident state that a whole pass over a split shares
 // (script/utility.py:90-101 evaluate_model, :103-121 evaluate_metric), in ONE launch per batch:
@@ -638,6 +746,107 @@ __global__ __launch_bounds__(1024) void eval_acc_kernel(EvalAccArgs a) {
     }
     if (lane == 0) {
         eval_finish(a, fv, k);
+        chain_st(ticket, 0u);
+    }
+}
+
+// ================================================================================================
+// The masked form (stgcn_eval_accumulate_masked): the sums of eval_acc_kernel over the OBSERVED labels of the counted windows (`valid`,
+// one byte per label, addressed as `target`), and two more:
+//     state[4] += observed elements             (a sum of ones here, not (B - first_valid) * N)
+//     state[5] += sum |d| / |y scale + mean|    (MAPE's numerator; an observed raw label of 0 makes it inf, as in the literature's code)
+// A masked element is selected out: whatever its label or prediction holds adds nothing.  The same thread-strided walk, butterfly, wave
+// order and ticket hand-off; six sums per workgroup, so the partial slabs are state[8 + 6 g ..].  With every label observed, words 0..4
+// take the very values eval_acc_kernel gives them.
+// ================================================================================================
+constexpr int kEvalMaskedSums = 6;
+__device__ __forceinline__ void eval_finish_masked(const EvalAccArgs& a, long k) {   // the position words only: the count is one of the sums
+    if (a.pos) {
+        const long done = (k + 1) * a.B;
+        const long start = done < a.num - a.B ? done : a.num - a.B;
+        a.pos[0] = start;
+        a.pos[1] = done - start < a.B ? done - start : a.B;
+        a.pos[2] = k + 1;
+    }
+}
+
+__global__ __launch_bounds__(1024) void eval_acc_masked_kernel(EvalAccArgs a, const uint8_t* valid) {
+    constexpr int S = kEvalMaskedSums;
+    extern __shared__ float stgcn_smem[];
+    double* red = reinterpret_cast<double*>(stgcn_smem);   // [16 waves][6]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long start = 0, fv = a.first_valid, k = 0;
+    if (a.pos) {
+        start = a.pos[0];
+        fv = a.pos[1];
+        k = a.pos[2];
+        start = start < 0 ? 0 : (start > a.num - a.B ? a.num - a.B : start);   // (never past the series, whatever the words hold)
+    }
+    fv = fv < 0 ? 0 : (fv > a.B ? a.B : fv);
+    const float* y = a.target + start * a.tstride;
+    const uint8_t* v = valid + start * a.tstride;
+    const long n = (long)a.B * a.N;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0;
+    for (long e = fv * a.N + (long)blockIdx.x * kEvalThreads + tid; e < n; e += (long)gridDim.x * kEvalThreads) {
+        const int node = (int)(e % a.N);
+        const float p = a.pred[e], t = y[e];
+        const bool ok = v[e] != 0;
+        const float sc = a.scale ? a.scale[node] : 1.0f, mu = a.mean ? a.mean[node] : 0.0f;
+        const float dz = p - t, d = (t - p) * sc, raw = t * sc + mu;
+        if (ok) {
+            s0 += (double)(dz * dz);
+            s1 += (double)fabsf(d);
+            s2 += (double)(d * d);
+            s3 += (double)raw;
+            s4 += 1.0;
+            s5 += (double)(fabsf(d) / fabsf(raw));
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        s0 += shfl_xor_f64(s0, m);
+        s1 += shfl_xor_f64(s1, m);
+        s2 += shfl_xor_f64(s2, m);
+        s3 += shfl_xor_f64(s3, m);
+        s4 += shfl_xor_f64(s4, m);
+        s5 += shfl_xor_f64(s5, m);
+    }
+    if (lane == 0) {
+        red[wave * S + 0] = s0;
+        red[wave * S + 1] = s1;
+        red[wave * S + 2] = s2;
+        red[wave * S + 3] = s3;
+        red[wave * S + 4] = s4;
+        red[wave * S + 5] = s5;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    double t = 0.0;   // lanes 0..5 of wave 0 own one sum each
+    if (lane < S)
+        for (int w = 0; w < kEvalThreads / 64; ++w) t += red[w * S + lane];
+    if (gridDim.x == 1) {
+        if (lane < S) a.state[lane] += t;
+        if (lane == 0) eval_finish_masked(a, k);
+        return;
+    }
+    if (lane < S) a.state[kEvalHdr + S * blockIdx.x + lane] = t;
+    unsigned* const ticket = reinterpret_cast<unsigned*>(a.state + 6);
+    chain_drain_stores();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    chain_drain_stores();   // (fence first, its own wait kept, then the ticket)
+    unsigned drawn = 0u;
+    if (lane == 0) drawn = chain_add(ticket, 1u);
+    drawn = __shfl(drawn, 0);
+    if (drawn != gridDim.x - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    chain_drain_stores();
+    if (lane < S) {
+        double tot = 0.0;
+        for (unsigned g = 0; g < gridDim.x; ++g) tot += a.state[kEvalHdr + S * g + lane];
+        a.state[lane] += tot;
+    }
+    if (lane == 0) {
+        eval_finish_masked(a, k);
         chain_st(ticket, 0u);
     }
 }

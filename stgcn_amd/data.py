@@ -185,6 +185,26 @@ def metrics_from_arrays(y_true: np.ndarray, y_pred: np.ndarray) -> Tuple[float, 
     return float(d.mean()), float(np.sqrt((d ** 2).mean())), float(d.sum() / np.asarray(y_true, dtype=np.float64).sum())
 
 
+def observed_mask(raw, null_val: float = 0.0) -> np.ndarray:
+    """The observed readings of a raw series as uint8 (1 = observed): NaN is always unobserved, and so is every reading equal to
+    ``null_val`` (a failed detector of METR-LA / PEMS-BAY / PeMSD7-M reports 0; DCRNN's and Graph WaveNet's masked metrics use
+    ``null_val = 0``).  ``null_val = nan``: NaN-coded series, only NaN is unobserved.  Take it from the RAW readings, before the z-score."""
+    a = np.asarray(raw, dtype=np.float64)
+    ok = ~np.isnan(a)
+    if not np.isnan(null_val):
+        ok &= a != null_val
+    return ok.astype(np.uint8)
+
+
+def masked_metrics_from_arrays(y_true: np.ndarray, y_pred: np.ndarray, valid: np.ndarray) -> Tuple[float, float, float, float]:
+    """MAE, RMSE, WMAPE and MAPE over the observed elements (``valid`` != 0) of inverse-transformed arrays: ``metrics_from_arrays``
+    restricted to them (masked elements are selected out, whatever they hold), plus MAPE = mean |y - p| / |y|."""
+    ok = np.asarray(valid).reshape(-1) != 0
+    y = np.asarray(y_true, dtype=np.float64).reshape(-1)[ok]
+    d = np.abs(y - np.asarray(y_pred, dtype=np.float64).reshape(-1)[ok])
+    return float(d.mean()), float(np.sqrt((d ** 2).mean())), float(d.sum() / y.sum()), float((d / np.abs(y)).mean())
+
+
 @torch.no_grad()
 def evaluate_metric(model, data_iter, scaler) -> Tuple[float, float, float]:
     """script/utility.py:103-121."""

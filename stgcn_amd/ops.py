@@ -58,7 +58,7 @@ def _check_device(t: torch.Tensor, what: str, activation: bool = False):
         raise RuntimeError(f"{what}: stgcn_amd runs on MI355X only (tensor is on {t.device}); there is no CPU fallback")
 
 
-_input_index: Dict[int, Tuple[torch.Tensor, int, Optional[torch.Tensor]]] = {}
+_input_index: Dict[int, tuple] = {}      # data_ptr of the bound view -> (index, stride, table, weak reference to the view)
 
 
 def bind_input_index(base: torch.Tensor, index: torch.Tensor, stride_floats: int, table: Optional[torch.Tensor] = None) -> None:
@@ -70,12 +70,22 @@ def bind_input_index(base: torch.Tensor, index: torch.Tensor, stride_floats: int
     ``table`` (int64 device tensor of window starts; shuffled epochs): window ``b`` of the batch is read
     ``table[index[0] + b] * stride_floats`` floats into ``base`` instead -- the position selects a run of table entries, not a run of
     consecutive windows (``x_window_dev`` / ``target_window_dev``).  The binding keeps the table alive; the caller keeps
-    ``index[0] + B`` within it and its entries inside the storage behind ``base``."""
+    ``index[0] + B`` within it and its entries inside the storage behind ``base``.
+
+    A binding lives as long as ``base`` does: it is keyed by an address, and once the view is gone the allocator may hand that address to
+    an unrelated tensor, which must not be read through a stale index word.  ``unbind_input_index`` drops it earlier."""
     assert index.dtype == torch.int64 and index.numel() == 1 and index.device == base.device
     if table is not None:
         if table.dtype != torch.int64 or table.dim() != 1 or not table.is_contiguous() or table.device != base.device:
             raise ValueError("bind_input_index: table must be a contiguous 1-D int64 tensor on the device of base")
-    _input_index[base.data_ptr()] = (index, int(stride_floats), table)
+    import weakref
+    key = base.data_ptr()
+
+    def _gone(ref, key=key):
+        e = _input_index.get(key)
+        if e is not None and e[3] is ref:
+            del _input_index[key]
+    _input_index[key] = (index, int(stride_floats), table, weakref.ref(base, _gone))
 
 
 def unbind_input_index(base: torch.Tensor) -> None:
@@ -289,12 +299,69 @@ def loss_kind_code(kind) -> int:
     return int(kind)
 
 
+class LossMask:
+    """The mask of a masked loss (``stgcn_loss_mask``): ``valid`` (uint8, 1 = observed, 0 = missing; a bool tensor is taken as it is, one
+    byte per element) over a label tensor or a whole resident series, and ``row_valid`` (int32), the observed labels of each label row of
+    ``row_elems`` labels (default: the last dimension, the nodes), formed here with ONE ``sum`` -- the launches add up the counts of their
+    own rows on the device, so no step pays for a count.  ``rows(lo, n)`` is the mask of label rows [lo, lo + n) as views of the same
+    storage; ``bind`` / ``unbind`` give ``valid`` the index word (and window table) of the label view it belongs to
+    (``bind_input_index``), so that the mask moves with the labels."""
+
+    def __init__(self, valid: torch.Tensor, row_elems: Optional[int] = None, _row_valid: Optional[torch.Tensor] = None):
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"mask: a bool or uint8 tensor expected, got {getattr(valid, 'dtype', type(valid))}")
+        if valid.dim() < 1 or valid.numel() < 1:
+            raise ValueError("mask: at least one label expected")
+        v = valid.detach().contiguous()
+        self.valid = v.view(torch.uint8) if v.dtype == torch.bool else v
+        self.row_elems = int(valid.shape[-1] if row_elems is None else row_elems)
+        if self.row_elems < 1 or self.valid.numel() % self.row_elems != 0:
+            raise ValueError(f"mask: {self.valid.numel()} labels are not whole rows of {self.row_elems}")
+        if _row_valid is None:
+            _row_valid = (self.valid != 0).reshape(-1, self.row_elems).sum(dim=1, dtype=torch.int32).contiguous()
+        self.row_valid = _row_valid
+
+    def rows(self, lo: int, n: int) -> "LossMask":
+        flat = self.valid.reshape(-1, self.row_elems)
+        if lo < 0 or n < 1 or lo + n > flat.shape[0]:
+            raise ValueError(f"mask: rows [{lo}, {lo + n}) outside the {flat.shape[0]} label rows")
+        return LossMask(flat[lo:lo + n], self.row_elems, self.row_valid[lo:lo + n])
+
+    def bind(self, index: torch.Tensor, stride: int, table: Optional[torch.Tensor] = None) -> None:
+        bind_input_index(self.valid, index, stride, table=table)
+
+    def unbind(self) -> None:
+        unbind_input_index(self.valid)
+
+    def struct(self) -> "_lib.LossMask":
+        m = _lib.LossMask()
+        m.valid, m.row_valid, m.row_elems = self.valid.data_ptr(), self.row_valid.data_ptr(), self.row_elems
+        return m
+
+
+def as_loss_mask(valid, target: torch.Tensor, what: str) -> LossMask:
+    """``valid=`` of a loss call as a ``LossMask`` checked against the labels: a bool / uint8 tensor of the target's shape (its counts are
+    formed here) or a ``LossMask`` over as many labels, on the target's device and with the target's index binding (``ValueError``)."""
+    mask = valid if isinstance(valid, LossMask) else LossMask(valid)
+    if not isinstance(valid, LossMask) and tuple(valid.shape) != tuple(target.shape):
+        raise ValueError(f"{what}: the mask has shape {tuple(valid.shape)}, the labels {tuple(target.shape)}")
+    if mask.valid.numel() != target.numel() or mask.valid.device != target.device:
+        raise ValueError(f"{what}: the mask covers {mask.valid.numel()} labels on {mask.valid.device}, the target has {target.numel()} on "
+                         f"{target.device}")
+    if _index_of(mask.valid) != _index_of(target):
+        raise ValueError(f"{what}: the mask and the labels must be bound to the same index word, stride and window table "
+                         f"(LossMask.bind beside bind_input_index of the label view)")
+    return mask
+
+
 def loss_and_grad(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: float = 1.0,
-                  grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+                  grad_scale: float = 1.0, valid=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The loss of ``kind`` ("mse": ``nn.MSELoss()``, main.py:136/167; "mae": ``nn.L1Loss()``; "huber": ``nn.HuberLoss(delta)``) and
     d loss / d pred in one launch (stgcn_loss_grad), outside autograd: the trainer calls ``pred.backward(dpred)`` instead of
     ``loss.backward()`` (main.py:168), which removes the five small ATen launches of the loss head.  Unlike torch's L1 backward a NaN
-    difference gives a NaN gradient element in every kind.  Returns (loss[1], dpred like pred)."""
+    difference gives a NaN gradient element in every kind.  ``valid`` (a bool / uint8 tensor of the target's shape or a ``LossMask``):
+    the loss and its gradient over the observed labels only (``stgcn_loss_grad_masked``; masked elements are selected out, their gradient
+    is exactly 0).  Returns (loss[1], dpred like pred)."""
     L = _lib.lib()
     code = loss_kind_code(kind)
     p = pred.detach()
@@ -304,6 +371,13 @@ def loss_and_grad(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: f
     loss = torch.empty(1, dtype=torch.float32, device=p.device)
     dpred = torch.empty_like(p)
     ti, tis, tw = _index_of(target)      # (tw, the window table: one window = one row of the leading dimension)
+    if valid is not None:
+        mask = as_loss_mask(valid, target, "loss_and_grad")
+        mst = mask.struct()
+        L.check(L.dll.stgcn_loss_grad_masked(code, float(delta), p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(),
+                                             dpred.data_ptr(), ti, tis, tw, 0 if tw is None else p.numel() // p.shape[0], C.byref(mst),
+                                             _stream_of(p)), "stgcn_loss_grad_masked")
+        return loss, dpred
     L.check(L.dll.stgcn_loss_grad(code, float(delta), p.data_ptr(), target.data_ptr(), p.numel(), float(grad_scale), loss.data_ptr(),
                                   dpred.data_ptr(), ti, tis, tw, 0 if tw is None else p.numel() // p.shape[0], _stream_of(p)),
             "stgcn_loss_grad")
@@ -316,11 +390,14 @@ def mse_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, grad_scale: floa
 
 
 EVAL_STATE_WORDS, EVAL_POS_WORDS = _lib.EVAL_STATE_WORDS, _lib.EVAL_POS_WORDS
+EVAL_MASKED_STATE_WORDS = _lib.EVAL_MASKED_STATE_WORDS
 
 
-def eval_state(device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """A zeroed metric state (float64, ``stgcn_eval_accumulate``'s layout) and zeroed position words (int64) on ``device``."""
-    return (torch.zeros(EVAL_STATE_WORDS, dtype=torch.float64, device=device), torch.zeros(EVAL_POS_WORDS, dtype=torch.int64, device=device))
+def eval_state(device, masked: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A zeroed metric state (float64, ``stgcn_eval_accumulate``'s layout; ``masked``: ``stgcn_eval_accumulate_masked``'s, six sums per
+    slab) and zeroed position words (int64) on ``device``."""
+    words = EVAL_MASKED_STATE_WORDS if masked else EVAL_STATE_WORDS
+    return (torch.zeros(words, dtype=torch.float64, device=device), torch.zeros(EVAL_POS_WORDS, dtype=torch.int64, device=device))
 
 
 def eval_arm(state: torch.Tensor, pos: Optional[torch.Tensor] = None) -> None:
@@ -330,9 +407,9 @@ def eval_arm(state: torch.Tensor, pos: Optional[torch.Tensor] = None) -> None:
     L.check(L.dll.stgcn_eval_arm(state.data_ptr(), _optr(pos), _stream_of(state)), "stgcn_eval_arm")
 
 
-def _check_eval_state(L, state: torch.Tensor, pos: Optional[torch.Tensor]) -> None:
-    if state.dtype != torch.float64 or state.numel() < EVAL_STATE_WORDS or not state.is_contiguous():
-        raise ValueError(f"evaluation state: {EVAL_STATE_WORDS} contiguous float64 words expected, got {state.numel()} x {state.dtype}")
+def _check_eval_state(L, state: torch.Tensor, pos: Optional[torch.Tensor], words: int = EVAL_STATE_WORDS) -> None:
+    if state.dtype != torch.float64 or state.numel() < words or not state.is_contiguous():
+        raise ValueError(f"evaluation state: {words} contiguous float64 words expected, got {state.numel()} x {state.dtype}")
     if pos is not None and (pos.dtype != torch.int64 or pos.numel() < EVAL_POS_WORDS or not pos.is_contiguous() or pos.device != state.device):
         raise ValueError(f"evaluation position: {EVAL_POS_WORDS} contiguous int64 words on the state's device expected")
     if L.is_emulator == state.is_cuda:
@@ -341,21 +418,32 @@ def _check_eval_state(L, state: torch.Tensor, pos: Optional[torch.Tensor]) -> No
 
 def eval_accumulate(pred: torch.Tensor, target: torch.Tensor, state: torch.Tensor, scale: Optional[torch.Tensor] = None,
                     mean: Optional[torch.Tensor] = None, first_valid: int = 0, pos: Optional[torch.Tensor] = None, num_windows: int = 0,
-                    target_stride: Optional[int] = None) -> None:
+                    target_stride: Optional[int] = None, valid: Optional[torch.Tensor] = None) -> None:
     """One minibatch of script/utility.py:90-121 added into ``state`` on the device (``stgcn_eval_accumulate``, one launch, nothing
     synchronises): ``pred`` (B, N) float32 predictions, ``target`` the (B, N) label rows (with ``pos`` the rows of window 0: the
     launch reads them ``pos[0] * target_stride`` floats further on and moves ``pos`` on to the next batch), ``scale`` / ``mean`` the
-    per-node inverse z-score or None.  Windows below ``first_valid`` are not counted."""
+    per-node inverse z-score or None.  Windows below ``first_valid`` are not counted.  ``valid`` (bool / uint8, the target's shape, read
+    where the target is read): only observed labels are scored, and the state (``eval_state(device, masked=True)``) also takes their count
+    and MAPE's sum (``stgcn_eval_accumulate_masked``)."""
     L = _lib.lib()
     p = pred.detach()
     _check_device(p, "pred")
-    _check_eval_state(L, state, pos)
+    _check_eval_state(L, state, pos, EVAL_STATE_WORDS if valid is None else EVAL_MASKED_STATE_WORDS)
     if p.dim() != 2 or not p.is_contiguous() or target.dtype != torch.float32 or not target.is_contiguous() or target.shape != p.shape:
         raise ValueError(f"eval_accumulate: contiguous float32 (B, N) tensors expected, got {tuple(p.shape)} / {tuple(target.shape)}")
     B, N = p.shape
     for t, what in ((scale, "scale"), (mean, "mean")):
         if t is not None and (t.dtype != torch.float32 or t.numel() != N or not t.is_contiguous() or t.device != p.device):
             raise ValueError(f"eval_accumulate: {what} must be {N} contiguous float32 values on {p.device}")
+    if valid is not None:
+        if (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != tuple(target.shape)
+                or not valid.is_contiguous() or valid.device != target.device):
+            raise ValueError(f"eval_accumulate: the mask must be a contiguous bool / uint8 tensor of the labels' shape {tuple(target.shape)} on "
+                             f"{target.device}, got {getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}")
+        L.check(L.dll.stgcn_eval_accumulate_masked(p.data_ptr(), target.data_ptr(), B, N, _optr(scale), _optr(mean), int(first_valid), _optr(pos),
+                                                   N if target_stride is None else int(target_stride), int(num_windows), state.data_ptr(),
+                                                   valid.data_ptr(), _stream_of(p)), "stgcn_eval_accumulate_masked")
+        return
     L.check(L.dll.stgcn_eval_accumulate(p.data_ptr(), target.data_ptr(), B, N, _optr(scale), _optr(mean), int(first_valid), _optr(pos),
                                         N if target_stride is None else int(target_stride), int(num_windows), state.data_ptr(),
                                         _stream_of(p)), "stgcn_eval_accumulate")
@@ -363,16 +451,21 @@ def eval_accumulate(pred: torch.Tensor, target: torch.Tensor, state: torch.Tenso
 
 def eval_metrics(words) -> dict:
     """The reference's numbers from the first five words of a metric state (host values): MSE in z-scored units
-    (utility.py:90-101), MAE / RMSE / WMAPE after the inverse transform (:111-121), and the element count."""
+    (utility.py:90-101), MAE / RMSE / WMAPE after the inverse transform (:111-121), and the element count.  Six or more words (a masked
+    state): the same over the observed elements, plus "mape" = words[5] / observed (NaN everywhere when nothing was observed)."""
     import math
     sse, sad, ssd, sy, n = (float(w) for w in words[:5])
+    if len(words) > 5:
+        if n <= 0:
+            return {"mse": math.nan, "mae": math.nan, "rmse": math.nan, "wmape": math.nan, "mape": math.nan, "elements": 0}
+        return {"mse": sse / n, "mae": sad / n, "rmse": math.sqrt(ssd / n), "wmape": sad / sy, "mape": float(words[5]) / n, "elements": int(n)}
     return {"mse": sse / n, "mae": sad / n, "rmse": math.sqrt(ssd / n), "wmape": sad / sy, "elements": int(n)}
 
 
 class _PendingLoss:
     """Loss waiting to be formed inside the head's backward (``stgcn_outblock_backward_loss``): ``loss_backward`` posts it, the
     ``_OutBlockFn.backward`` that receives the placeholder gradient takes it."""
-    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "window", "grad_scale", "loss", "kind", "delta")
+    __slots__ = ("placeholder", "pred", "target", "index", "index_stride", "window", "grad_scale", "loss", "kind", "delta", "mask")
 
 
 _pending_loss: Optional[_PendingLoss] = None
@@ -390,21 +483,25 @@ def _head_node_of(pred: torch.Tensor):
     return fn if fn is not None and type(fn).__name__ == "_OutBlockFnBackward" else None
 
 
-def loss_backward(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: float = 1.0, grad_scale: float = 1.0) -> torch.Tensor:
+def loss_backward(pred: torch.Tensor, target: torch.Tensor, kind="mse", delta: float = 1.0, grad_scale: float = 1.0,
+                  valid=None) -> torch.Tensor:
     """``l = nn.MSELoss()(pred, target); l.backward()`` (main.py:167-168; ``kind``: as in ``loss_and_grad``) for a prediction that comes
     straight out of the fused output head: the seed gradient is formed inside the head's fc backward kernel and the loss value comes out of
     the step's gradient reduction (no loss launch at all).  Any other ``pred`` takes the one-launch loss kernel (``loss_and_grad``) followed
-    by ``pred.backward(dpred)``.  Returns the loss (shape [1]); with an active gradient sink it is valid after the sink's flush."""
+    by ``pred.backward(dpred)``.  ``valid``: as in ``loss_and_grad`` -- the fused path hands the mask to the same fc backward launch
+    (``stgcn_outblock_backward_loss_masked``), the two-call path to the loss launch.  Returns the loss (shape [1]); with an active gradient
+    sink it is valid after the sink's flush."""
     global _pending_loss
     code = loss_kind_code(kind)
     p = pred.detach()
     if (_head_node_of(pred) is None or not p.is_contiguous() or p.shape != target.shape or not target.is_contiguous()
             or target.dtype != torch.float32 or os.environ.get("STGCN_FUSED_LOSS", "1") == "0"):
-        loss, dpred = loss_and_grad(pred, target, code, delta, grad_scale)
+        loss, dpred = loss_and_grad(pred, target, code, delta, grad_scale, valid=valid)
         pred.backward(dpred)
         return loss
     _check_device(p, "pred")
     pl = _PendingLoss()
+    pl.mask = None if valid is None else as_loss_mask(valid, target, "loss_backward")
     pl.placeholder = torch.empty_like(p)            # never written, never read: its address identifies the request
     pl.pred, pl.target, pl.grad_scale = p, target, float(grad_scale)
     pl.kind, pl.delta = code, float(delta)
@@ -916,10 +1013,18 @@ class _OutBlockFn(torch.autograd.Function):
             hl.target_window_dev = fused_loss.window
             hl.kind, hl.delta = fused_loss.kind, fused_loss.delta
             ctx.keep_loss = fused_loss                  # the buffers outlive a deferred reduction
-            L.check(L.dll.stgcn_outblock_backward_loss(C.byref(desc), C.byref(pst), x_cl.data_ptr(), C.byref(hl), saved.data_ptr(),
-                                                       ctx.ws.data_ptr(), C.byref(gst), None if dx is None else dx.data_ptr(),
-                                                       None if ih is None else C.byref(ih.hook), _stream_of(x_cl)),
-                    "stgcn_outblock_backward_loss")
+            if fused_loss.mask is not None:
+                mst = fused_loss.mask.struct()
+                L.check(L.dll.stgcn_outblock_backward_loss_masked(C.byref(desc), C.byref(pst), x_cl.data_ptr(), C.byref(hl), C.byref(mst),
+                                                                  saved.data_ptr(), ctx.ws.data_ptr(), C.byref(gst),
+                                                                  None if dx is None else dx.data_ptr(),
+                                                                  None if ih is None else C.byref(ih.hook), _stream_of(x_cl)),
+                        "stgcn_outblock_backward_loss_masked")
+            else:
+                L.check(L.dll.stgcn_outblock_backward_loss(C.byref(desc), C.byref(pst), x_cl.data_ptr(), C.byref(hl), saved.data_ptr(),
+                                                           ctx.ws.data_ptr(), C.byref(gst), None if dx is None else dx.data_ptr(),
+                                                           None if ih is None else C.byref(ih.hook), _stream_of(x_cl)),
+                        "stgcn_outblock_backward_loss")
         else:
             L.check(L.dll.stgcn_outblock_backward_hook(C.byref(desc), C.byref(pst), x_cl.data_ptr(), dout.data_ptr(), saved.data_ptr(),
                                                        ctx.ws.data_ptr(), C.byref(gst), None if dx is None else dx.data_ptr(),

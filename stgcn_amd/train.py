@@ -208,13 +208,14 @@ def check_loss(loss: str, huber_delta: float = 1.0) -> None:
         raise ValueError(f"huber_delta = {huber_delta} must be finite and positive")
 
 
-def fwd_loss_bwd(model, x, y, loss: str = "mse", huber_delta: float = 1.0):
+def fwd_loss_bwd(model, x, y, loss: str = "mse", huber_delta: float = 1.0, valid=None):
     """forward -> loss (MSELoss: main.py:166-168) -> backward with the loss formed inside the fused head's backward (``ops.loss_backward``;
-    one loss launch + ``pred.backward(dpred)`` for a model without the fused head).  Returns the loss (shape [])."""
+    one loss launch + ``pred.backward(dpred)`` for a model without the fused head).  ``valid`` (bool / uint8 like ``y``, or an
+    ``ops.LossMask``): the mean over the observed labels only (``data.observed_mask``).  Returns the loss (shape [])."""
     from . import ops
     check_loss(loss, huber_delta)
     y_pred = model(x).reshape(len(x), -1)
-    return ops.loss_backward(y_pred, y, loss, huber_delta)[0]
+    return ops.loss_backward(y_pred, y, loss, huber_delta, valid=valid)[0]
 
 
 def check_in_launch_waits(model) -> None:
@@ -271,11 +272,12 @@ class GradArena:
 
 
 def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, all_reduce=None, loss: str = "mse",
-                     huber_delta: float = 1.0):
+                     huber_delta: float = 1.0, valid=None):
     """The loop body of main.py:165-169 with the step tail fused: forward -> backward with the loss (``loss``) formed inside the head and
     deferred reductions -> ONE launch for all gradient reductions + AdamW (world == 1), or reductions into the flat arena ->
     ``all_reduce(arena.flat)`` -> AdamW (world > 1; the 1/world of the gradient mean rides on the loss gradient).
-    ``param.grad`` are the arena views (overwritten every step, never accumulated)."""
+    ``param.grad`` are the arena views (overwritten every step, never accumulated).  ``valid``: as in ``fwd_loss_bwd``; with
+    world > 1 each rank takes the mean over its own observed labels and the ranks are averaged, as DDP around a masked mean does."""
     from . import ops
     check_loss(loss, huber_delta)
     if not fused_tail_supported(model, arena.params):
@@ -284,7 +286,7 @@ def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, a
     arena.install()
     with ops.grad_sink_scope(arena.sink):
         y_pred = model(x).reshape(len(x), -1)
-        value = ops.loss_backward(y_pred, y, loss, huber_delta, grad_scale=1.0 / world)      # (valid after the flush below)
+        value = ops.loss_backward(y_pred, y, loss, huber_delta, grad_scale=1.0 / world, valid=valid)      # (valid after the flush below)
     if world <= 1 and hasattr(optimizer, "flush_with"):
         optimizer.flush_with(arena.sink, arena.grads)
     else:
@@ -295,13 +297,14 @@ def fused_train_step(model, optimizer, x, y, arena: GradArena, world: int = 1, a
     return value[0]
 
 
-def train_step(model, optimizer, x, y, allreduce: Optional[FlatGradAllReduce] = None, loss: str = "mse", huber_delta: float = 1.0):
-    """zero_grad -> forward -> loss (MSELoss) -> backward -> [all-reduce] -> optimizer.step (main.py:165-169).
-    Returns the loss tensor (no host sync: the reference's per-step .item() at main.py:170 is deferred)."""
+def train_step(model, optimizer, x, y, allreduce: Optional[FlatGradAllReduce] = None, loss: str = "mse", huber_delta: float = 1.0,
+               valid=None):
+    """zero_grad -> forward -> loss (MSELoss) -> backward -> [all-reduce] -> optimizer.step (main.py:165-169).  ``valid``: as in
+    ``fwd_loss_bwd``.  Returns the loss tensor (no host sync: the reference's per-step .item() at main.py:170 is deferred)."""
     from .layers import DropoutStream
     check_loss(loss, huber_delta)
     optimizer.zero_grad(set_to_none=True)
-    value = fwd_loss_bwd(model, x, y, loss, huber_delta)
+    value = fwd_loss_bwd(model, x, y, loss, huber_delta, valid=valid)
     if allreduce is not None:
         allreduce()
     optimizer.step()
@@ -309,15 +312,20 @@ def train_step(model, optimizer, x, y, allreduce: Optional[FlatGradAllReduce] = 
     return value.detach()
 
 
-def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0, loss: str = "mse", huber_delta: float = 1.0):
+def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0, loss: str = "mse", huber_delta: float = 1.0, valid=None):
     """The partial last minibatch of an epoch (the reference iterates with ``DataLoader(drop_last=False)``, main.py:126-131, so its
     last step sees n < batch_size windows).  ``x`` / ``y`` are the GLOBAL tail batch (n windows, the same tensors on every rank);
     rank r takes a contiguous share of ceil(n / world) windows -- possibly none -- and weights its loss gradient by n_local / n, so
     the SUM all-reduce of the gradients is exactly the gradient of the mean loss over the n windows (``weight by local count``,
-    SURVEY.md section 8e; every loss kind is a mean).  Eager launches: a captured step has a fixed batch shape.  Returns the global mean loss (tensor)."""
+    SURVEY.md section 8e; every loss kind is a mean).  Eager launches: a captured step has a fixed batch shape.  Returns the global mean loss (tensor).
+    ``valid`` (bool / uint8 like ``y``): the masked mean, for world == 1 only -- with a mask the weight of a rank's share is its OBSERVED
+    count over the batch's, a device value that the host-side n_local / n cannot stand in for (``NotImplementedError`` for world > 1)."""
     from . import ops
     from .layers import DropoutStream
     check_loss(loss, huber_delta)
+    if valid is not None and world > 1:
+        raise NotImplementedError("tail_step: valid= with world > 1 is not implemented: the weight of a rank's share of a masked mean is its "
+                                  "observed count over the batch's, not n_local / n")
     n = len(x)
     per = (n + world - 1) // world
     lo, hi = min(rank * per, n), min(rank * per + per, n)
@@ -340,7 +348,8 @@ def tail_step(model, optimizer, x, y, world: int = 1, rank: int = 0, loss: str =
     try:
         if hi > lo:
             pred = model(x[lo:hi]).reshape(hi - lo, -1)
-            value = ops.loss_backward(pred, y[lo:hi].contiguous(), loss, huber_delta, grad_scale=(hi - lo) / n)
+            value = ops.loss_backward(pred, y[lo:hi].contiguous(), loss, huber_delta, grad_scale=(hi - lo) / n,
+                                      valid=None if valid is None else valid[lo:hi].contiguous())
             loss_sum = value * ((hi - lo) / n)
     finally:
         if folded is not None:
@@ -468,9 +477,15 @@ class GraphedTrainStep:
     def __init__(self, model, optimizer, x_example: torch.Tensor, y_example: torch.Tensor, world: int = 1, warmup: int = 3,
                  chains: int = 1, fused: Optional[bool] = None, series: Optional[torch.Tensor] = None, n_his: int = 12,
                  n_pred: int = 3, rank: int = 0, capture_collective: bool = False, shuffle: bool = False, shuffle_seed: int = 0,
-                 loss: str = "mse", huber_delta: float = 1.0):
+                 loss: str = "mse", huber_delta: float = 1.0, valid: Optional[torch.Tensor] = None):
         """``loss`` / ``huber_delta``: the loss the step trains on ("mse", "mae", "huber": ``LOSSES``), frozen into the capture like every
         other kernel argument.  An unknown name is refused here, not at the first step.
+
+        ``valid`` (with ``series``): a (time, N) bool or uint8 tensor over the rows of ``series``, 1 = observed (``data.observed_mask``).
+        The step then trains on the observed labels only: the mask stays resident beside the series and is read through the same index
+        word and the same ``WindowOrder`` table as the labels, and the head's fc backward launch forms the batch's observed count from a
+        per-row table built here once -- the launches of the step are those of the unmasked step.  Needs ``series=``; refused with
+        ``chains > 1`` (the chained path forms its loss with torch).  Both are a ``ValueError`` here.
 
         ``series``: optional resident (time, N) float32 device tensor (already z-scored).  The step then takes its windows
         straight from it (device-side windowing): window b of the minibatch is rows
@@ -492,11 +507,16 @@ class GraphedTrainStep:
         (``probe_collective_capture``: a capture that hangs instead of raising would otherwise take the run with it)."""
         from .layers import DropoutStream
         check_loss(loss, huber_delta)
+        if valid is not None and series is None:
+            raise ValueError("valid= needs the resident series (series=...): the mask is read through the labels' index word")
+        if valid is not None and int(chains) > 1:
+            raise ValueError("valid= with chains > 1 is not supported: the chained path forms its loss outside the fused head")
         assert x_example.is_cuda, "hipGraph capture needs the MI355X path"
         self.model, self.opt, self.world = model, optimizer, world
         self.loss_kind, self.huber_delta = loss, float(huber_delta)
         dev = x_example.device
         self.series, self.index, self._index_bump = series, None, None
+        self.mask = None                          # ops.LossMask view over the label rows of the batch (valid=)
         self._order: Optional[WindowOrder] = None
         if shuffle and series is None:
             raise ValueError("shuffle=True needs the resident series (series=...)")
@@ -537,6 +557,13 @@ class GraphedTrainStep:
             table = None if self._order is None else self._order.order
             ops.bind_input_index(self.x, self.index, N, table=table)
             ops.bind_input_index(self.y, self.index, N, table=table)
+            if valid is not None:
+                if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != tuple(series.shape):
+                    raise ValueError(f"valid: a bool / uint8 tensor of the series' shape {tuple(series.shape)} expected, got "
+                                     f"{getattr(valid, 'dtype', type(valid))} {tuple(getattr(valid, 'shape', ()))}")
+                self.mask_series = ops.LossMask(valid.to(dev), N)       # resident; row_valid: one int32 per series row
+                self.mask = self.mask_series.rows(n_his + n_pred - 1, B)      # the rows of self.y
+                self.mask.bind(self.index, N, table=table)
         if DropoutStream.counter is None or DropoutStream.counter.device != dev:
             DropoutStream.use_device_counter(dev)
         self.counter = DropoutStream.counter     # the captured kernels hold this address: keep it alive with the graph
@@ -649,6 +676,8 @@ class GraphedTrainStep:
         if self.series is not None:
             ops.unbind_input_index(self.x)
             ops.unbind_input_index(self.y)
+            if self.mask is not None:
+                self.mask.unbind()
         if DropoutStream.counter is self.counter:
             DropoutStream.disable_device_counter()
         if hasattr(self.opt, "trainer_owns_step"):
@@ -664,7 +693,7 @@ class GraphedTrainStep:
     def _fwd_bwd(self):
         if self.chains > 1:
             return chained_fwd_bwd(self.model, self.x, self.y, self.chains, self.streams, self.loss_kind, self.huber_delta)
-        return fwd_loss_bwd(self.model, self.x, self.y, self.loss_kind, self.huber_delta)
+        return fwd_loss_bwd(self.model, self.x, self.y, self.loss_kind, self.huber_delta, valid=self.mask)
 
     def _fused_fwd_bwd(self):
         """forward, one-launch loss + gradient (carrying the 1/world of the gradient mean), backward with deferred reductions;
@@ -674,7 +703,7 @@ class GraphedTrainStep:
         with ops.grad_sink_scope(self.arena.sink):
             y_pred = self.model(self.x).reshape(len(self.x), -1)
             loss = ops.loss_backward(y_pred, self.y, self.loss_kind, self.huber_delta,
-                                     grad_scale=1.0 / self.world)      # (written by the gradient flush of the step)
+                                     grad_scale=1.0 / self.world, valid=self.mask)      # (written by the gradient flush of the step)
         if self.world > 1:
             self.arena.sink.flush(stream=torch.cuda.current_stream(self.x.device).cuda_stream)
         return loss[0]
@@ -774,9 +803,12 @@ class GraphedEvalPass:
     optimizer's step counter nor ``model._step_counters`` (an eval-mode forward hands no counters to the pack launch), and its position
     words are its own.  A captured graph holds the addresses of the model's workspaces, which ``ops.WorkspaceCache`` reallocates when a
     plan grows: the constructor refuses (RuntimeError, before anything moved) if its forward would grow an existing workspace, and holds
-    on to the buffers its own graph uses.  ``close()`` / the context manager drop the index bindings."""
+    on to the buffers its own graph uses.  ``close()`` / the context manager drop the index bindings.
 
-    def __init__(self, model, series, n_his: int, n_pred: int, batch_size: int, scaler=None, capture: bool = True):
+    ``valid``: a (rows, N) bool / uint8 array or tensor over ``series``, 1 = observed.  The pass then scores the observed labels only
+    (``stgcn_eval_accumulate_masked``, still one launch per batch) and ``run()`` also returns "mape" and "elements" (observed)."""
+
+    def __init__(self, model, series, n_his: int, n_pred: int, batch_size: int, scaler=None, capture: bool = True, valid=None):
         import numpy as np
         from . import _lib, ops
         self.model, self.B, self.n_his, self.n_pred = model, int(batch_size), int(n_his), int(n_pred)
@@ -799,7 +831,15 @@ class GraphedEvalPass:
         self.series_x = self.series if cd in (None, self.series.dtype) else self.series.to(cd)
         self.x = torch.as_strided(self.series_x, (B, 1, self.n_his, N), (N, self.n_his * N, N, 1))     # window b = rows [b, b + n_his)
         self.y = self.series[self.n_his + self.n_pred - 1:self.n_his + self.n_pred - 1 + B]            # label rows of windows 0 .. B-1
-        self.state, self.pos = ops.eval_state(dev)
+        self.valid = self.valid_y = None
+        if valid is not None:
+            v = valid if torch.is_tensor(valid) else torch.as_tensor(np.asarray(valid))
+            if v.dtype not in (torch.bool, torch.uint8) or tuple(v.shape) != tuple(self.series.shape):
+                raise ValueError(f"GraphedEvalPass: valid must be a bool / uint8 mask of the series' shape {tuple(self.series.shape)}, got "
+                                 f"{v.dtype} {tuple(v.shape)}")
+            self.valid = v.detach().to(dev).contiguous().view(torch.uint8) if v.dtype == torch.bool else v.detach().to(dev).contiguous()
+            self.valid_y = self.valid[self.n_his + self.n_pred - 1:self.n_his + self.n_pred - 1 + B]      # beside self.y, moved by pos like it
+        self.state, self.pos = ops.eval_state(dev, masked=self.valid is not None)
         self.scale = self.mean = None
         if scaler is not None:
             self.scale = torch.as_tensor(np.asarray(scaler.scale_, dtype=np.float32).reshape(-1)).to(dev).contiguous()
@@ -879,10 +919,11 @@ class GraphedEvalPass:
             pred = self.model(self.x).reshape(self.B, -1)
             if pred.dtype != torch.float32 or not pred.is_contiguous():
                 pred = pred.float().contiguous()
-            ops.eval_accumulate(pred, self.y, self.state, self.scale, self.mean, pos=self.pos, num_windows=self.num)
+            ops.eval_accumulate(pred, self.y, self.state, self.scale, self.mean, pos=self.pos, num_windows=self.num, valid=self.valid_y)
 
     def run(self) -> dict:
-        """One pass over the split: {"mse", "mae", "rmse", "wmape"} as the reference defines them (floats) and "windows" (int)."""
+        """One pass over the split: {"mse", "mae", "rmse", "wmape"} as the reference defines them (floats) and "windows" (int).  With
+        ``valid``: the same over the observed labels, plus "mape", "elements" (observed labels) and "windows" (all scored windows)."""
         from . import ops
         model = self.model
         was_training = model.training
@@ -895,11 +936,14 @@ class GraphedEvalPass:
             else:
                 for _ in range(self.batches):
                     self._batch()
-            words = self.state[:5].cpu()             # the pass's one synchronisation and one device-to-host copy
+            words = self.state[:5 if self.valid is None else 6].cpu()      # the pass's one synchronisation and one device-to-host copy
         finally:
             model.train(was_training)
         check_in_launch_waits(model)                 # (where the numbers are read)
         m = ops.eval_metrics(words.tolist())
+        if self.valid is not None:
+            m["windows"] = self.num
+            return m
         n = m.pop("elements")
         m["windows"] = n // self.series.shape[1]
         return m

@@ -14,7 +14,10 @@ One JSON line per epoch and one for the test metrics; a persistence forecast
 (y_hat = last observed value) on the same windows is printed beside them for scale.
 
   python tools/train_demo.py [--epochs 3] [--n-pred 3] [--rows 34272] [--opt adamw | nadamw | lion] [--shuffle]
-                             [--loss mse | mae | huber] [--huber-delta 1.0]
+                             [--loss mse | mae | huber] [--huber-delta 1.0] [--missing FRAC] [--null-val V]
+
+--missing FRAC zeroes a seeded random share of the synthetic readings (failed detectors report 0); --null-val V masks the readings equal
+to V (and NaN) in training and in both evaluation passes (masked loss and metrics; the JSON rows gain "mape" and "observed").
 """
 import argparse
 import json
@@ -52,6 +55,10 @@ def main():
     ap.add_argument("--huber-delta", type=float, default=1.0)
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="clip the gradient by its global norm inside the captured step (clip_grad_norm_ + step); the log gains grad_norm / clip_coef")
+    ap.add_argument("--missing", type=float, default=0.0,
+                    help="zero out this share of the synthetic readings (seeded), as failed detectors do; 0 = the plain series")
+    ap.add_argument("--null-val", type=float, default=None,
+                    help="train and score on observed readings only: readings equal to this value (and NaN) are masked; nan = NaN-coded")
     a = ap.parse_args()
 
     from stgcn_amd import DropoutStream, data, models
@@ -62,6 +69,9 @@ def main():
     gso_np = np.load(os.path.join(ROOT, "tests", "golden", "gso_real.npz"))["metr_la.cheb_sym_norm_lap"]
     n = gso_np.shape[0]
     vel = synthetic_speeds(a.rows, n)
+    if a.missing > 0:
+        vel[np.random.default_rng(1).uniform(size=vel.shape) < a.missing] = 0.0
+    ok = None if a.null_val is None else data.observed_mask(vel, a.null_val)      # from the raw readings, before the z-score
     len_train, len_val, len_test = data.split_lengths(a.rows)
     zs = data.ZScore()
     train = zs.fit_transform(vel[:len_train])
@@ -79,11 +89,15 @@ def main():
     x0 = torch.zeros(BS, 1, N_HIS, n, device=dev)
     y0 = torch.zeros(BS, n, device=dev)
     # the evaluation passes first: their graphs keep the workspaces they captured, and the training step's constructor may still grow them
-    val_pass = GraphedEvalPass(model, val, N_HIS, a.n_pred, BS)
-    test_pass = GraphedEvalPass(model, test, N_HIS, a.n_pred, BS, scaler=zs)
+    ok_train = ok_val = ok_test = None
+    if ok is not None:
+        ok_train, ok_val, ok_test = ok[:len_train], ok[len_train:len_train + len_val], ok[len_train + len_val:]
+    # (masked: the validation pass gets the scaler too, so that its MAPE is in the data's units; val_loss, the z-scored MSE, does not depend on it)
+    val_pass = GraphedEvalPass(model, val, N_HIS, a.n_pred, BS, scaler=zs if ok is not None else None, valid=ok_val)
+    test_pass = GraphedEvalPass(model, test, N_HIS, a.n_pred, BS, scaler=zs, valid=ok_test)
     model.train()
     step = GraphedTrainStep(model, opt, x0, y0, series=series, n_his=N_HIS, n_pred=a.n_pred, shuffle=a.shuffle, shuffle_seed=42,
-                            loss=a.loss, huber_delta=a.huber_delta)
+                            loss=a.loss, huber_delta=a.huber_delta, valid=None if ok is None else torch.from_numpy(ok_train).to(dev))
     windows = series.shape[0] - N_HIS - a.n_pred + 1
     steps_per_epoch = windows // BS
     first_epoch_steps = steps_per_epoch
@@ -110,11 +124,14 @@ def main():
             step.reshuffle()                    # the next epoch's permutation, written into the table the graph already reads
         opt.sync_lr()                           # the captured AdamW reads its learning rate from device memory
         t0 = time.perf_counter()
-        val_loss = val_pass.run()["mse"]        # one synchronise per pass (script/utility.py:90-101 on the device)
+        vm = val_pass.run()                     # one synchronise per pass (script/utility.py:90-101 on the device)
+        val_loss = vm["mse"]
         eval_s = time.perf_counter() - t0
         row = {"epoch": epoch + 1, "train_loss": round(float(acc.item()) / n_steps, 6), "val_loss": round(val_loss, 6),
                "lr": opt.param_groups[0]["lr"], "steps": n_steps, "epoch_s": round(el, 3), "eval_s": round(eval_s, 3),
                "train_windows_per_s": round(n_steps * BS / el, 1)}
+        if ok is not None:
+            row.update(mape=round(vm["mape"], 6), observed=vm["elements"])
         if a.max_grad_norm is not None:         # of the epoch's last step (device words of the clip state)
             row.update(grad_norm=round(float(opt.last_grad_norm.item()), 6), clip_coef=round(float(opt.last_clip_coef.item()), 6))
         print(json.dumps(row), flush=True)
@@ -126,8 +143,14 @@ def main():
     for x, y in test_s.batches(BS):
         ys.append(zs.inverse_transform(y.cpu().numpy()).reshape(-1))
         ps.append(zs.inverse_transform(x[:, 0, -1, :].cpu().numpy()).reshape(-1))
-    p_mae, p_rmse, p_wmape = data.metrics_from_arrays(np.concatenate(ys), np.concatenate(ps))
-    print(json.dumps({"test": {"MAE": round(mae, 4), "RMSE": round(rmse, 4), "WMAPE": round(wmape, 6)},
+    test_row = {"MAE": round(mae, 4), "RMSE": round(rmse, 4), "WMAPE": round(wmape, 6)}
+    if ok is None:
+        p_mae, p_rmse, p_wmape = data.metrics_from_arrays(np.concatenate(ys), np.concatenate(ps))
+    else:                                       # the persistence forecast on the same observed labels
+        shift = N_HIS + a.n_pred - 1
+        p_mae, p_rmse, p_wmape, _ = data.masked_metrics_from_arrays(np.concatenate(ys), np.concatenate(ps), ok_test[shift:shift + len(test_s)])
+        test_row.update(mape=round(m["mape"], 6), observed=m["elements"])
+    print(json.dumps({"test": test_row,
                       "persistence_forecast": {"MAE": round(p_mae, 4), "RMSE": round(p_rmse, 4), "WMAPE": round(p_wmape, 6)},
                       "test_windows": len(test_s), "n_pred": a.n_pred, "data": "synthetic METR-LA-shaped speeds, real METR-LA graph"}), flush=True)
 
