@@ -30,7 +30,7 @@ extern "C" {
 
 /* ABI revision: bumped whenever an entry point changes its argument list or a struct its layout (round 3 added `y` to the
  * backward entry points and `stored_US2` to the plan: 1 -> 2 in effect, never recorded; round 4: stgcn_set_gemm_big_nt, the
- * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9; the loss kinds: stgcn_head_loss.kind / .delta, stgcn_loss_grad: 10).  Entry points that are only ADDED leave the number alone -- clipping by global norm (stgcn_grad_clip, stgcn_grad_norm, stgcn_optim_step_clip, stgcn_grad_flush_clip, the two state queries) changed no argument list and no layout: still 10; a library from before them lacks the symbols, and a binding that needs them finds that out when it looks them up.  stgcn_version() returns the value the LIBRARY was built with; a binding built
+ * chained-launch control words in `ws`: 3, then 4; round 5: stgcn_set_chain_spin_ticks, stgcn_outblock_chain_status: 5; round 6: stgcn_set_tc2ln_peers, stgcn_stblock_chain_status, stgcn_prepack_park / _flush, the exchange words of tmp_conv2 + LayerNorm in `ws`: 6; stgcn_optim_step, stgcn_grad_flush_optim: 7; stgcn_eval_accumulate, stgcn_eval_arm: 8; x_window_dev, target_window_dev, stgcn_mse_loss_grad_windows: 9; the loss kinds: stgcn_head_loss.kind / .delta, stgcn_loss_grad: 10).  Entry points that are only ADDED leave the number alone -- clipping by global norm (stgcn_grad_clip, stgcn_grad_norm, stgcn_optim_step_clip, stgcn_grad_flush_clip, the two state queries) changed no argument list and no layout: still 10; a library from before them lacks the symbols, and a binding that needs them finds that out when it looks them up; likewise the sparse graph shift operator (STGCN_GC_CHEB_CSR / STGCN_GC_KIPF_CSR, stgcn_gso_csr_*): new enum values an older library refuses and new symbols, no layout touched: still 10.  stgcn_version() returns the value the LIBRARY was built with; a binding built
  * against another header must refuse to run (stgcn_amd/_lib.py does).                                                  */
 #define STGCN_ABI_VERSION 10
 
@@ -43,6 +43,14 @@ extern "C" {
 #define STGCN_ACT_GTU 1 /* tanh(P + R) * sigmoid(Q)   layers.py:109 */
 #define STGCN_GC_CHEB 0 /* cheb_graph_conv            layers.py:143-172 */
 #define STGCN_GC_KIPF 1 /* graph_conv                 layers.py:194-206 */
+/* The same two graph convs with a SPARSE graph shift operator: gso_pad / gso_t_pad of stgcn_stblock_forward / _backward / _backward_hook
+ * then point to CSR blobs of L and L^T written by stgcn_gso_csr_prepare (below), not to dense matrices.  The block runs the recursion
+ * X_k = 2 L X_{k-1} - X_{k-2} on the activations for ANY node count (the "tiled" route: plan.tiled_gc = 1, NP = roundup16(N),
+ * ws_XT empty), one gathered product per term (gso_spmm_kernel, stgcn_kernels_gcsparse.hip.h): work and memory follow nnz, not N^2.
+ * Operator values stay fp32 and sums are fp32 for both activation types; no atomics, results are bitwise reproducible.
+ * Every entry point that takes a descriptor derives the same route from these values.                                            */
+#define STGCN_GC_CHEB_CSR 2
+#define STGCN_GC_KIPF_CSR 3
 
 /* Storage / arithmetic type of the ACTIVATIONS of a call (desc.dtype).  Parameters, their gradients, LayerNorm statistics, the
  * partial-sum arena, optimizer state and the head's prediction are fp32 in both modes.
@@ -191,6 +199,23 @@ int stgcn_gso_prepare(const float* gso, int32_t N, int32_t terms, float* gso_pad
  * Chebyshev recursion of layers.py:153-161 then runs on the activations, one GEMM launch per term
  * (stgcn_kernels_gctile.hip.h).                                                                                         */
 int stgcn_gso_layout(int32_t N, int32_t terms, int64_t* NP, int64_t* mats, int64_t* scratch_mats, int32_t* tiled);
+
+/* ---- Sparse graph shift operator (graph_conv = STGCN_GC_CHEB_CSR / STGCN_GC_KIPF_CSR).
+ *   stgcn_gso_csr_layout   size of a blob in floats for N nodes and nnz stored entries (1 <= N <= 32768, 0 <= nnz <= N * N).
+ *   stgcn_gso_csr_prepare  rowptr (N + 1 int32), col (nnz int32), val (nnz fp32): DEVICE arrays of one CSR matrix whose columns are
+ *                          sorted and unique within each row (explicit zeros, empty rows and rows of any length are fine).  Writes the
+ *                          blob -- 4-byte words: 16 header words {magic, N, nnz, 0..}, rowptr, col, val, each padded to a multiple of
+ *                          4 words -- and REGISTERS its address.  The call SYNCHRONISES `stream` and checks the index arrays on the
+ *                          host first (rowptr from 0 to nnz and monotone, 0 <= col < N, sorted and unique): STGCN_ERR_INVALID
+ *                          otherwise, nothing written, nothing registered.  Call it once for L and once for L^T (the backward
+ *                          gathers too: it reads CSR(L^T), never scatters).
+ *   stgcn_gso_csr_release  forgets a blob (before its memory is freed or reused).
+ * Registry rule: the library keeps pointer -> (N, nnz, longest row) for the blobs it prepared.  A block call with a CSR graph_conv whose
+ * operator pointer is not registered, or was prepared for another N, returns STGCN_ERR_INVALID BEFORE it launches anything -- a dense
+ * operator handed over by mistake is never read as column indices.  The caller keeps a registered blob unchanged.              */
+int stgcn_gso_csr_layout(int32_t N, int64_t nnz, int64_t* blob_floats);
+int stgcn_gso_csr_prepare(const int32_t* rowptr, const int32_t* col, const float* val, int32_t N, int64_t nnz, float* blob, void* stream);
+int stgcn_gso_csr_release(const float* blob);
 
 /* Test knob: 1 = the fused kernels also write the intermediates they normally keep on chip (dZ2 -> ws_dZ2) so that stage tests
  * can compare them with the oracle.  Returns the previous value; other values only query.                                  */

@@ -18,6 +18,7 @@ STGCN_OK = 0
 ABI_VERSION = 10     # include/stgcn_hip.h: STGCN_ABI_VERSION (tests/test_capi_symbols.py keeps the two equal)
 ACT = {"glu": 0, "gtu": 1}
 GRAPH_CONV = {"cheb_graph_conv": 0, "graph_conv": 1}
+GRAPH_CONV_CSR = {"cheb_graph_conv": 2, "graph_conv": 3}      # STGCN_GC_CHEB_CSR / STGCN_GC_KIPF_CSR: the operator is a CSR blob
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LOSS = {"mse": 0, "mae": 1, "huber": 2}      # STGCN_LOSS_*
 EVAL_STATE_WORDS, EVAL_POS_WORDS = 264, 4     # STGCN_EVAL_STATE_WORDS (fp64), STGCN_EVAL_POS_WORDS (int64)
@@ -273,6 +274,15 @@ class _Lib:
                                                           C.POINTER(LossMask), C.c_void_p, C.c_void_p, C.POINTER(OutblockGrads), C.c_void_p,
                                                           C.POINTER(LnHook), C.c_void_p]
         d.stgcn_eval_accumulate_masked.argtypes = d.stgcn_eval_accumulate.argtypes[:-1] + [C.c_void_p, C.c_void_p]
+        # (the sparse graph shift operator: new enum values and entries, added at ABI revision 10 without a bump)
+        for f in ("stgcn_gso_csr_layout", "stgcn_gso_csr_prepare", "stgcn_gso_csr_release"):
+            if not hasattr(d, f):
+                raise StgcnError(f"{path} does not export {f} (built before the sparse graph shift operator was added): rebuild with "
+                                 f"`python -m stgcn_amd.build --force`")
+            getattr(d, f).restype = C.c_int
+        d.stgcn_gso_csr_layout.argtypes = [C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        d.stgcn_gso_csr_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+        d.stgcn_gso_csr_release.argtypes = [C.c_void_p]
         d.stgcn_profile_enable.argtypes = [C.c_int]
         d.stgcn_profile_enable.restype = C.c_int
         d.stgcn_profile_collect.argtypes = [C.c_char_p, C.c_size_t]
@@ -321,4 +331,5 @@ EXPORTED_SYMBOLS = ["stgcn_version", "stgcn_backend", "stgcn_last_error", "stgcn
                     "stgcn_set_chain_spin_ticks", "stgcn_outblock_chain_status", "stgcn_set_tc2ln_peers", "stgcn_stblock_chain_status", "stgcn_prepack_park", "stgcn_prepack_flush",
                     "stgcn_optim_step", "stgcn_grad_flush_optim", "stgcn_eval_arm", "stgcn_eval_accumulate", "stgcn_loss_grad",
                     "stgcn_grad_clip_words", "stgcn_grad_flush_clip_words", "stgcn_grad_norm", "stgcn_optim_step_clip", "stgcn_grad_flush_clip",
-                    "stgcn_loss_grad_masked", "stgcn_outblock_backward_loss_masked", "stgcn_eval_accumulate_masked"]
+                    "stgcn_loss_grad_masked", "stgcn_outblock_backward_loss_masked", "stgcn_eval_accumulate_masked",
+                    "stgcn_gso_csr_layout", "stgcn_gso_csr_prepare", "stgcn_gso_csr_release"]

@@ -8,10 +8,14 @@
 #include <stdlib.h>
 #include <math.h>
 #include <string.h>
+#include <map>
+#include <mutex>
+#include <vector>
 
 #include "stgcn_kernels_bwd.hip.h"
 #include "stgcn_kernels_fwd.hip.h"
 #include "stgcn_kernels_gctile.hip.h"
+#include "stgcn_kernels_gcsparse.hip.h"
 #include "stgcn_kernels_gcslab16.hip.h"
 #include "stgcn_kernels_head.hip.h"
 #include "stgcn_route.h"
@@ -125,10 +129,10 @@ int check_desc(const stgcn_stblock_desc* d) {
     if (!d) return fail(STGCN_ERR_INVALID, "desc is NULL");
     if (d->B < 1 || d->T < 1 || d->N < 1 || d->c_in < 1) return fail(STGCN_ERR_INVALID, "B/T/N/c_in must be positive");
     if (d->Kt < 1) return fail(STGCN_ERR_INVALID, "Kt must be >= 1");
-    if (d->graph_conv == STGCN_GC_CHEB && d->Ks < 1)
+    if ((d->graph_conv == STGCN_GC_CHEB || d->graph_conv == STGCN_GC_CHEB_CSR) && d->Ks < 1)
         return fail(STGCN_ERR_INVALID, "ERROR: the graph convolution kernel size Ks has to be a positive integer, but received %d.", d->Ks);
     if (d->act != STGCN_ACT_GLU && d->act != STGCN_ACT_GTU) return fail(STGCN_ERR_INVALID, "act must be glu or gtu");
-    if (d->graph_conv != STGCN_GC_CHEB && d->graph_conv != STGCN_GC_KIPF) return fail(STGCN_ERR_INVALID, "bad graph_conv enum");
+    if (d->graph_conv != STGCN_GC_CHEB && d->graph_conv != STGCN_GC_KIPF && !gc_is_csr(d->graph_conv)) return fail(STGCN_ERR_INVALID, "bad graph_conv enum");
     if (d->T - 2 * (d->Kt - 1) < 1) return fail(STGCN_ERR_INVALID, "T=%d too short for two Kt=%d temporal convs", d->T, d->Kt);
     if (!(d->droprate >= 0.f && d->droprate < 1.f)) return fail(STGCN_ERR_INVALID, "droprate must be in [0, 1)");   // (this form refuses NaN too)
     if (!(d->c0 == 64 || d->c0 == 128) || !(d->c2 == 64 || d->c2 == 128))
@@ -139,7 +143,7 @@ int check_desc(const stgcn_stblock_desc* d) {
     if ((int64_t)d->B * (d->T - d->Kt + 1) > 65535)   // per-slab launches index the (b, t) slab with blockIdx.y
         return fail(STGCN_ERR_UNSUPPORTED, "B*(T-Kt+1) = %lld (b, t) slabs exceed the 65535 rows of a launch grid: split the batch",
                     (long long)d->B * (d->T - d->Kt + 1));
-    if (d->graph_conv == STGCN_GC_CHEB && d->Ks > 8) return fail(STGCN_ERR_UNSUPPORTED, "Ks=%d > 8", d->Ks);
+    if (!gc_is_kipf(d->graph_conv) && d->Ks > 8) return fail(STGCN_ERR_UNSUPPORTED, "Ks=%d > 8", d->Ks);
     if ((d->c_in & 3) != 0 && d->Kt * d->c_in > 16)
         return fail(STGCN_ERR_UNSUPPORTED, "c_in=%d: input channels must be a multiple of 4 unless Kt*c_in <= 16", d->c_in);
     if (d->dtype != STGCN_DTYPE_F32 && d->dtype != STGCN_DTYPE_BF16) return fail(STGCN_ERR_INVALID, "dtype must be STGCN_DTYPE_F32 or STGCN_DTYPE_BF16");
@@ -465,12 +469,46 @@ int launch_gso_gemm_bf16(const char* label, const float* Mpad, OperandBuf x, flo
     return STGCN_OK;
 }
 
-int launch_gconv_fwd_tiled(const GconvFwdArgs& a, hipStream_t st) {
+// ---- sparse operator (stgcn_kernels_gcsparse.hip.h) ---------------------------------------------------------------------------------------
+// Host-side registry of the blobs stgcn_gso_csr_prepare wrote: pointer -> N, nnz, longest row.  A CSR call whose operator is not in it,
+// or was prepared for another N, is refused before anything is launched: the kernel follows column indices, and a dense buffer handed
+// over by mistake must never be read as such.
+struct CsrInfo { int N; long nnz; int longest; };
+std::mutex g_csr_mu;
+std::map<const void*, CsrInfo> g_csr_blobs;
+int csr_lookup(const char* who, const float* blob, int N, CsrInfo* info) {
+    std::lock_guard<std::mutex> lk(g_csr_mu);
+    const auto it = g_csr_blobs.find(blob);
+    if (it == g_csr_blobs.end()) return fail(STGCN_ERR_INVALID, "%s: the operator at %p is not a blob of stgcn_gso_csr_prepare (sparse graph_conv)", who, (const void*)blob);
+    if (it->second.N != N) return fail(STGCN_ERR_INVALID, "%s: the sparse operator was prepared for N = %d, the call has N = %d", who, it->second.N, N);
+    *info = it->second;
+    return STGCN_OK;
+}
+// out = alpha * M X + b1 * Z1 + b2 * Z2 with M the registered blob (launch_gso_gemm's contract)
+int launch_gso_spmm(const char* label, const float* blob, const float* X, float alpha, const float* Z1, float b1, const float* Z2, float b2,
+                    float* out, int N, long slabs, hipStream_t st) {
+    CsrInfo ci;
+    const int rc = csr_lookup(label, blob, N, &ci);
+    if (rc) return rc;
+    GsoSpmmArgs g = zeroed<GsoSpmmArgs>();
+    g.rowptr = reinterpret_cast<const int*>(blob + kCsrHdr);
+    g.col = reinterpret_cast<const int*>(blob + csr_off_col(N));
+    g.val = blob + csr_off_val(N, ci.nnz);
+    g.X = X; g.Z1 = Z1; g.Z2 = Z2; g.out = out; g.alpha = alpha; g.b1 = b1; g.b2 = b2;
+    g.N = N; g.slabs = slabs;
+    g.nodes_per_wg = spmm_nodes_per_wg();
+    g.node_chunks = cdiv(N, g.nodes_per_wg);
+    g.slab_groups = cdiv(slabs, kSpSlabs);
+    STGCN_LAUNCH_ET(label, st, (gso_spmm_kernel<ET>), dim3((unsigned)(g.node_chunks * g.slab_groups)), dim3(256), 0, g);
+    return STGCN_OK;
+}
+
+int launch_gconv_fwd_tiled(const GconvFwdArgs& a, hipStream_t st, bool sparse = false) {
     if (a.Ks > kGcMaxTerms) return fail(STGCN_ERR_UNSUPPORTED, "tiled graph conv with %d terms (supported: up to %d)", a.Ks, kGcMaxTerms);
     if (a.Ks > 1 && !a.Xk) return fail(STGCN_ERR_INVALID, "tiled graph conv needs the X_k buffers");
     const long ks = a.slabs * a.N * 16;                 // elements per term
     const long ksf = g_bf16 ? ks / 2 : ks;              // ... in the 4-byte units of the float* slots
-    const bool bf = (g_gc_precision > 0 || g_bf16) && a.Ks > 1;   // bf16 activations: the operator products run on the bf16 matrix cores
+    const bool bf = !sparse && (g_gc_precision > 0 || g_bf16) && a.Ks > 1;   // bf16 activations: the operator products run on the bf16 matrix cores
     if (bf && !a.XT) return fail(STGCN_ERR_INVALID, "tiled graph conv (bf16 operator products) needs the operand workspace");
     const long CP = gc_operand_cols(a.slabs);
     if (bf) {
@@ -483,7 +521,9 @@ int launch_gconv_fwd_tiled(const GconvFwdArgs& a, hipStream_t st) {
         const float* Xm2 = k == 1 ? nullptr : (k == 2 ? a.A : a.Xk + (size_t)(k - 3) * ksf);
         float* out = a.Xk + (size_t)(k - 1) * ksf;
         int rc;
-        if (bf) {
+        if (sparse) {
+            rc = launch_gso_spmm("gso_spmm_fwd", a.Lp, Xm1, k == 1 ? 1.f : 2.f, Xm2, -1.f, nullptr, 0.f, out, a.N, a.slabs, st);
+        } else if (bf) {
             const OperandBuf next = operand_buf(a.XT, k & 1, CP, a.NP);   // term k reads buffer (k - 1) & 1
             rc = launch_gso_gemm_bf16("gso_gemm_fwd", a.Lp, operand_buf(a.XT, (k - 1) & 1, CP, a.NP), k == 1 ? 1.f : 2.f, Xm2, -1.f, nullptr, 0.f,
                                       out, k + 1 < a.Ks ? &next : nullptr, a.N, a.NP, a.slabs, st);
@@ -502,7 +542,7 @@ int launch_gconv_fwd_tiled(const GconvFwdArgs& a, hipStream_t st) {
 }
 // backward: row pass (g_k, parameter-gradient partials), then dA = sum_k T_k(L^T) g_k by the Clenshaw recurrence
 //     b_K = g_K ; b_k = g_k + 2 L^T b_{k+1} - b_{k+2} (in place over g_k) ; dA = g_0 + L^T b_1 - b_2
-int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st) {
+int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st, bool sparse = false) {
     if (a.Ks > kGcMaxTerms) return fail(STGCN_ERR_UNSUPPORTED, "tiled graph conv with %d terms (supported: up to %d)", a.Ks, kGcMaxTerms);
     if (!a.Gk || a.wgs < 1 || a.tiles_per_wg < 1) return fail(STGCN_ERR_INVALID, "tiled graph-conv backward: missing workspace / geometry");
     const long ks = a.slabs * a.N * 16;                 // elements per term
@@ -515,6 +555,13 @@ int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st) {
     STGCN_LAUNCH_ET("gconv_rows_bwd", st, (gconv_rows_bwd_kernel<ET>), dim3((unsigned)a.wgs), dim3(256), gc_rows_bwd_lds_bytes(r.terms), r);
     if (K == 0) return STGCN_OK;
     auto gk = [&](int k) { return a.Gk + (size_t)k * ksf; };
+    if (sparse) {   // the same recurrence, the products gathered from CSR(L^T)
+        for (int k = K - 1; k >= 1; --k) {
+            const int rc = launch_gso_spmm("gso_spmm_bwd", a.LTp, gk(k + 1), 2.f, gk(k), 1.f, k + 2 <= K ? gk(k + 2) : nullptr, -1.f, gk(k), a.N, a.slabs, st);
+            if (rc) return rc;
+        }
+        return launch_gso_spmm("gso_spmm_bwd", a.LTp, gk(1), 1.f, gk(0), 1.f, K >= 2 ? gk(2) : nullptr, -1.f, a.dA, a.N, a.slabs, st);
+    }
     if (g_gc_precision > 0 || g_bf16) {   // bf16 / bf16x3 products: b_{k+1} travels in operand form from epilogue to epilogue
         if (!a.XT) return fail(STGCN_ERR_INVALID, "tiled graph-conv backward (bf16 operator products) needs the operand workspace");
         const long CP = gc_operand_cols(a.slabs);
@@ -539,8 +586,8 @@ int launch_gconv_bwd_tiled(const GconvBwdArgs& a, hipStream_t st) {
     return launch_gso_gemm("gso_gemm_bwd", a.LTp, gk(1), 1.f, gk(0), 1.f, K >= 2 ? gk(2) : nullptr, -1.f, a.dA, a.N, a.NP, a.slabs, st);
 }
 
-int launch_gconv_fwd(GconvFwdArgs a, bool tiled, hipStream_t st) {
-    if (tiled) return launch_gconv_fwd_tiled(a, st);
+int launch_gconv_fwd(GconvFwdArgs a, bool tiled, hipStream_t st, bool sparse = false) {
+    if (tiled) return launch_gconv_fwd_tiled(a, st, sparse);
     const int HT = a.NP / 16;
     int pf = (HT + 3) / 4, pb = 1;
     gc_parts_override(pf, pb);
@@ -598,8 +645,8 @@ inline int gcbwd2_job_waves(int Ks, int parts, int nwa) {
     const int want = (Ks + 1 + parts - 1) / parts, room = 768 / 64 - nwa;
     return want < room ? want : room;
 }
-int launch_gconv_bwd(GconvBwdArgs a, bool tiled, hipStream_t st) {
-    if (tiled) return launch_gconv_bwd_tiled(a, st);
+int launch_gconv_bwd(GconvBwdArgs a, bool tiled, hipStream_t st, bool sparse = false) {
+    if (tiled) return launch_gconv_bwd_tiled(a, st, sparse);
     const int HT = a.NP / 16;
     int pf = 0, pb = 1;
     gc_parts_override(pf, pb);
@@ -779,7 +826,7 @@ void reduce_jobs_block(ReduceList& L, const stgcn_stblock_desc* d, const BlockRo
         L.add(G->al_w, ap, Pn, ps, 1, d->c0, d->c1, 0, d->c1, 1, 0, 1, d->c0);   // enumerate (i, j): src dWa[i][j] -> dst al_w[j][i]
         L.add_flat(G->al_b, ap + (long)d->c0 * d->c1, Pn, ps, d->c1);
     }
-    if (d->graph_conv == STGCN_GC_KIPF) L.add_flat(G->gc_w, part + bg.off_gc + 256, bg.gc_count, bg.gc_stride, 256);
+    if (gc_is_kipf(d->graph_conv)) L.add_flat(G->gc_w, part + bg.off_gc + 256, bg.gc_count, bg.gc_stride, 256);
     else L.add_flat(G->gc_w, part + bg.off_gc, bg.gc_count, bg.gc_stride, v.terms * 256);
     L.add_flat(G->gc_b, part + bg.off_gc + (long)v.terms * 256, bg.gc_count, bg.gc_stride, 16);
     const int n = d->N * d->c2;
@@ -866,7 +913,7 @@ void carve_plan(const stgcn_stblock_desc* d, const BlockRoute& v, stgcn_stblock_
     p->ws_dZ1 = take(act(v.rows1 * v.NC1));
     p->tiled_gc = v.tiled_gc;
     p->ws_Gk = take(v.tiled_gc ? (int64_t)v.terms * act(v.rows1 * d->c1) : 0);
-    p->ws_XT = take(v.tiled_gc && v.terms > 1 ? 2 * gc_operand_alloc(v.slabs1) * (int64_t)gc_plane_ld(v.NP) : 0);
+    p->ws_XT = take(v.tiled_gc && !v.sparse_gc && v.terms > 1 ? 2 * gc_operand_alloc(v.slabs1) * (int64_t)gc_plane_ld(v.NP) : 0);
     p->part_floats = v.bg.total;
     p->ws_part = take(p->part_floats);
     p->ws_floats = o;
@@ -975,9 +1022,9 @@ struct BlockCall {
         GconvFwdArgs gc = zeroed<GconvFwdArgs>();
         gc.A = saved + pl.sv_A; gc.Lp = gso_pad; gc.W = P->gc_w; gc.bias = P->gc_b;
         gc.Xk = saved + pl.sv_Xk; gc.G = saved + pl.sv_G;
-        gc.N = d->N; gc.NP = r.NP; gc.Ks = r.terms; gc.kipf = d->graph_conv == STGCN_GC_KIPF; gc.slabs = r.slabs1;
-        gc.XT = r.tiled_gc && r.terms > 1 ? ws + pl.ws_XT : nullptr;
-        return launch_gconv_fwd(gc, r.tiled_gc, st);
+        gc.N = d->N; gc.NP = r.NP; gc.Ks = r.terms; gc.kipf = gc_is_kipf(d->graph_conv); gc.slabs = r.slabs1;
+        gc.XT = r.tiled_gc && !r.sparse_gc && r.terms > 1 ? ws + pl.ws_XT : nullptr;
+        return launch_gconv_fwd(gc, r.tiled_gc, st, r.sparse_gc);
     }
     // tmp_conv2 + gate + LayerNorm([N, c2]) + dropout in one launch: tc2_ln_peers workgroups per (b, t2) slab
     int launch_tc2_ln_fwd(float* y) {
@@ -1155,6 +1202,55 @@ int stgcn_gso_prepare(const float* gso, int32_t N, int32_t terms, float* gso_pad
     return STGCN_OK;
 }
 
+int stgcn_gso_csr_layout(int32_t N, int64_t nnz, int64_t* blob_floats) {
+    if (N < 1 || N > 32768 || nnz < 0 || nnz > (int64_t)N * N || nnz >= (1ll << 31) || !blob_floats)
+        return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_layout: bad arguments (1 <= N <= 32768, 0 <= nnz <= N * N, nnz < 2^31)");
+    *blob_floats = csr_blob_floats(N, nnz);
+    return STGCN_OK;
+}
+
+int stgcn_gso_csr_prepare(const int32_t* rowptr, const int32_t* col, const float* val, int32_t N, int64_t nnz, float* blob, void* stream) {
+    int64_t words = 0;
+    const int rc = stgcn_gso_csr_layout(N, nnz, &words);
+    if (rc) return rc;
+    if (!rowptr || !blob || (nnz > 0 && (!col || !val))) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: NULL array");
+    hipStream_t st = (hipStream_t)stream;
+    // the index arrays are checked HERE, on the host, before a blob can be registered: nothing else stands between a bad index and a gather
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(STGCN_ERR_LAUNCH, "stgcn_gso_csr_prepare: stream synchronisation failed");
+    std::vector<int32_t> rp((size_t)N + 1), cl((size_t)nnz);
+    if (hipMemcpy(rp.data(), rowptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        (nnz > 0 && hipMemcpy(cl.data(), col, cl.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(STGCN_ERR_LAUNCH, "stgcn_gso_csr_prepare: reading the index arrays failed");
+    if (rp[0] != 0 || rp[N] != nnz) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: rowptr must run from 0 to nnz = %lld (got %d .. %d)", (long long)nnz, rp[0], rp[N]);
+    int longest = 0;
+    for (int n = 0; n < N; ++n) {   // all of rowptr first: the column walk below indexes `cl` through it
+        if (rp[n + 1] < rp[n]) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: rowptr decreases at row %d", n);
+        if (rp[n + 1] > nnz) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: rowptr of row %d runs past nnz = %lld", n, (long long)nnz);
+        if (rp[n + 1] - rp[n] > longest) longest = rp[n + 1] - rp[n];
+    }
+    for (int n = 0; n < N; ++n) {
+        for (int e = rp[n]; e < rp[n + 1]; ++e) {
+            if (cl[e] < 0 || cl[e] >= N) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: column %d of row %d outside [0, %d)", cl[e], n, N);
+            if (e > rp[n] && cl[e] <= cl[e - 1]) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_prepare: columns of row %d are not sorted and unique", n);
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_csr_mu);
+        g_csr_blobs.erase(blob);   // (a blob prepared again is not valid while it is being rewritten)
+    }
+    STGCN_LAUNCH("gso_csr_pack", st, gso_csr_pack_kernel, dim3(cdiv(words, kThreads) < 1024 ? cdiv(words, kThreads) : 1024), dim3(kThreads), 0, rowptr, col, val,
+                 (int)N, (int)nnz, blob);
+    std::lock_guard<std::mutex> lk(g_csr_mu);
+    g_csr_blobs[blob] = CsrInfo{(int)N, (long)nnz, longest};
+    return STGCN_OK;
+}
+
+int stgcn_gso_csr_release(const float* blob) {
+    std::lock_guard<std::mutex> lk(g_csr_mu);
+    if (!g_csr_blobs.erase(blob)) return fail(STGCN_ERR_INVALID, "stgcn_gso_csr_release: %p is not a registered blob", (const void*)blob);
+    return STGCN_OK;
+}
+
 int stgcn_dropout_mask(float* out, int64_t n, float droprate, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream) {
     if (!out || n < 0 || (n & 3)) return fail(STGCN_ERR_INVALID, "stgcn_dropout_mask: n must be a non-negative multiple of 4");
     // at p = 1 the keep scale is inf and a draw of 0xFFFFFFFF is still kept (drop_thresh clamps to 2^32 - 1); NaN fails both compares
@@ -1198,6 +1294,11 @@ int stgcn_stblock_forward(const stgcn_stblock_desc* d, const stgcn_stblock_param
     if (d->c_in > d->c0 && !P->tc1_aw) return fail(STGCN_ERR_INVALID, "tc1_aw required when c_in > c0");
     if (d->c0 > d->c1 && !P->al_w) return fail(STGCN_ERR_INVALID, "al_w required when c0 > c1");
     if (d->c1 > d->c2 && !P->tc2_aw) return fail(STGCN_ERR_INVALID, "tc2_aw required when c1 > c2");
+    if (c.r.sparse_gc) {   // the operator must be a registered blob for this N: refused before the first launch
+        CsrInfo ci;
+        rc = csr_lookup("stgcn_stblock_forward", gso_pad, d->N, &ci);
+        if (rc) return rc;
+    }
     g_prof_tag = d->reserved;
     g_bf16 = c.r.bf16;
 

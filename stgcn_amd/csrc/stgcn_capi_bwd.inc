@@ -96,10 +96,10 @@ struct BlockBwdCall : BlockCall {
         GconvBwdArgs a = zeroed<GconvBwdArgs>();
         a.dY = ws + pl.ws_dYg; a.X0 = saved + pl.sv_A; a.Xk = saved + pl.sv_Xk; a.LTp = gso_t_pad; a.W = P->gc_w;
         a.dA = ws + pl.ws_dA; a.part = part() + r.bg.off_gc; a.N = d->N; a.NP = r.NP; a.Ks = r.terms;
-        a.kipf = d->graph_conv == STGCN_GC_KIPF; a.slabs = r.slabs1;
+        a.kipf = gc_is_kipf(d->graph_conv); a.slabs = r.slabs1;
         a.Gk = r.tiled_gc ? ws + pl.ws_Gk : nullptr; a.tiles_per_wg = r.bg.gc_tiles_per_wg; a.wgs = r.bg.gc_count;
-        a.XT = r.tiled_gc && r.terms > 1 ? ws + pl.ws_XT : nullptr;
-        return launch_gconv_bwd(a, r.tiled_gc, st);
+        a.XT = r.tiled_gc && !r.sparse_gc && r.terms > 1 ? ws + pl.ws_XT : nullptr;
+        return launch_gconv_bwd(a, r.tiled_gc, st, r.sparse_gc);
     }
     // Align + gate backward on its own: dZ1 and the Align partials (BWD_STAGED; the stage tests' dZ1 beside BWD_FUSED, whose dWa partials it
     // sends to their own, then unused, slot).  Gate inputs as stored by the forward, or recomputed from x (K <= 16)
@@ -201,6 +201,11 @@ int stgcn_stblock_backward_hook(const stgcn_stblock_desc* d, const stgcn_stblock
     if (d->need_dx && !dx) return fail(STGCN_ERR_INVALID, "stgcn_stblock_backward: need_dx set but dx is NULL");
     rc = check_dx_hook("stgcn_stblock_backward", dx_hook, d->N, d->c_in, d->need_dx, d->dtype);
     if (rc) return rc;
+    if (c.r.sparse_gc) {   // the transposed operator must be a registered blob for this N: refused before the block's first launch
+        CsrInfo ci;
+        rc = csr_lookup("stgcn_stblock_backward", gso_t_pad, d->N, &ci);
+        if (rc) return rc;
+    }
     g_prof_tag = d->reserved;
     g_bf16 = c.r.bf16;
 

@@ -173,6 +173,18 @@ inline bool gc_is_tiled(int N, int terms) {
     return ((long)terms * 16 * (NP + 4) + NP * 20) * (long)sizeof(float) > 160 * 1024;
 }
 inline int gc_padded_nodes(int N, int terms) { return gc_is_tiled(N, terms) ? (N + kGtBM - 1) / kGtBM * kGtBM : (N + 15) / 16 * 16; }
+// Sparse operator (graph_conv = STGCN_GC_*_CSR; stgcn_kernels_gcsparse.hip.h): the recursion of the tiled path for ANY node count, its
+// operator products through gso_spmm_kernel.  No dense matrix, hence no padded node count beyond the row tiles' (NP = roundup16(N)) and
+// no bf16 operand form (ws_XT = 0).  Decided here, from the descriptor alone, so that every entry point that re-derives the route agrees.
+inline bool gc_is_csr(int graph_conv) { return graph_conv == STGCN_GC_CHEB_CSR || graph_conv == STGCN_GC_KIPF_CSR; }
+inline bool gc_is_kipf(int graph_conv) { return graph_conv == STGCN_GC_KIPF || graph_conv == STGCN_GC_KIPF_CSR; }
+// destination nodes per workgroup of gso_spmm_kernel: 4, one node per wave.  STGCN_SPMM_NODES (read once; a multiple of 4) is the knob
+// the sweep of profiles/sparse_gc_cost.md is made with.  Measured at the C5 block-0 shape, 16 entries per row, fp32 / bf16 us per launch:
+// 4 nodes 234 / 132, 8: 242 / 138, 16: 252 / 145, 32: 264 / 155, 64: 290 / 185 -- short workgroups, many of them in flight per CU
+inline int spmm_nodes_per_wg() {
+    static const int v = [] { const int e = env_int("STGCN_SPMM_NODES", 4); return e < 4 ? 4 : e > 1024 ? 1024 : e / 4 * 4; }();
+    return v;
+}
 
 // ================================================================================================
 // Geometry of the backward launches and of the partial-sum arena
@@ -226,7 +238,7 @@ inline WgradGeom wgrad_geom(long rows, int K, int NC, long off, int target_wgs =
     return g;
 }
 
-inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, int Kt, int terms, int need_dx) {
+inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, int Kt, int terms, int need_dx, bool sparse_gc = false) {
     BwdGeom g;
     const int T1 = T - Kt + 1, T2 = T1 - Kt + 1;
     const long rows1 = (long)B * T1 * N, rows2 = (long)B * T2 * N, slabs1 = (long)B * T1, slabs2 = (long)B * T2;
@@ -266,7 +278,7 @@ inline BwdGeom bwd_geom(int B, int T, int N, int c_in, int c0, int c1, int c2, i
     g.gc_stride = (terms + 1) * 256;
     g.gc_count = (int)slabs1;
     g.gc_tiles_per_wg = 0;
-    if (gc_is_tiled(N, terms)) {   // ~1024 workgroups, whole groups of 4 tiles (one per wave)
+    if (sparse_gc || gc_is_tiled(N, terms)) {   // ~1024 workgroups, whole groups of 4 tiles (one per wave)
         const long tiles16 = (rows1 + 15) / 16;
         long per = (tiles16 + 1023) / 1024;
         per = (per + 3) / 4 * 4;
@@ -333,6 +345,7 @@ struct BlockRoute {
     bool tc1_bwd_x6;
     size_t tc1_bwd_lds;
     bool tiled_gc;           // graph conv on the tiled GEMM path
+    bool sparse_gc;          // ... its operator products from a CSR operator (gso_spmm_kernel); implies tiled_gc
     bool bf16_bwd_ok;        // (bf16 calls) every backward stage of this route has a bf16 instance: see bf16_backward_ok
 };
 
@@ -347,9 +360,10 @@ inline BlockRoute route_block(const stgcn_stblock_desc* d) {
     BlockRoute r;
     r.T1 = d->T - d->Kt + 1;
     r.T2 = r.T1 - d->Kt + 1;
-    r.terms = d->graph_conv == STGCN_GC_KIPF ? 2 : d->Ks;
-    r.tiled_gc = gc_is_tiled(d->N, r.terms);
-    r.NP = gc_padded_nodes(d->N, r.terms);
+    r.terms = gc_is_kipf(d->graph_conv) ? 2 : d->Ks;
+    r.sparse_gc = gc_is_csr(d->graph_conv);
+    r.tiled_gc = r.sparse_gc || gc_is_tiled(d->N, r.terms);
+    r.NP = r.sparse_gc ? (d->N + 15) / 16 * 16 : gc_padded_nodes(d->N, r.terms);
     r.KP1 = (int)rup((int64_t)d->Kt * d->c_in, 16);
     r.KP2 = (int)rup((int64_t)d->Kt * d->c1, 16);
     r.NC1 = 2 * d->c0;
@@ -362,7 +376,7 @@ inline BlockRoute route_block(const stgcn_stblock_desc* d) {
     r.slabs1 = (int64_t)d->B * r.T1;
     r.slabs2 = (int64_t)d->B * r.T2;
     r.bf16 = d->dtype == STGCN_DTYPE_BF16;
-    r.bg = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, r.terms, d->need_dx);
+    r.bg = bwd_geom(d->B, d->T, d->N, d->c_in, d->c0, d->c1, d->c2, d->Kt, r.terms, d->need_dx, r.sparse_gc);
     const bool x6 = mfma_x6() && !r.bf16;
     const bool tc1_fwd_ok = tc1_fwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt), tc1_bwd_ok = tc1_bwd_shape_ok(d->c_in, d->c0, d->c1, d->Kt);
     // ---- packs

@@ -86,8 +86,16 @@ def calc_chebynet_gso(gso, lambda_max: str = "scipy_norm2", seed=None):
     return 2 * gso / eig - ident
 
 
-def gso_tensor(gso, device) -> torch.Tensor:
-    """main.py:101-103: dense float32 operator on the device (what ``args.gso`` holds)."""
+def gso_tensor(gso, device, sparse: bool = False) -> torch.Tensor:
+    """main.py:101-103: dense float32 operator on the device (what ``args.gso`` holds).  ``sparse=True``: the same operator as a
+    ``torch.sparse_csr`` tensor (sorted columns, duplicates summed) without ever forming the dense matrix -- a model built with it runs the
+    sparse graph conv, whose memory and work follow the stored entries."""
+    if sparse:
+        m = sp.csr_matrix(gso, dtype=np.float32)
+        m.sum_duplicates()
+        m.sort_indices()
+        return torch.sparse_csr_tensor(torch.from_numpy(m.indptr.astype(np.int64)), torch.from_numpy(m.indices.astype(np.int64)),
+                                       torch.from_numpy(m.data.astype(np.float32)), size=m.shape).to(device)
     dense = gso.toarray() if sp.issparse(gso) else np.asarray(gso)
     return torch.from_numpy(dense.astype(np.float32)).to(device)
 

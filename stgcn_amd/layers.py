@@ -237,7 +237,7 @@ class STConvBlock(nn.Module):
         self.dropout = nn.Dropout(p=droprate)
         self.cfg = ops.BlockConfig(Kt=Kt, Ks=Ks, n_vertex=n_vertex, c_in=last_block_channel, channels=tuple(channels),
                                    act_func=act_func, graph_conv_type=graph_conv_type, droprate=float(droprate),
-                                   ln_eps=self.tc2_ln.eps)
+                                   ln_eps=self.tc2_ln.eps, sparse_gso=ops.is_sparse_gso(gso))
         self.gso = gso                      # plain attribute like the reference: not in state_dict, not moved by .to()
         self._gso_cache = None              # (key, padded, padded transposed)
         self._ws = ops.WorkspaceCache()
@@ -245,7 +245,17 @@ class STConvBlock(nn.Module):
 
     def _operators(self, device):
         gso = self.gso
-        key = (gso.data_ptr(), gso._version, str(device), ops.gc_layout_epoch())
+        sparse = ops.is_sparse_gso(gso)
+        if sparse != self.cfg.sparse_gso:
+            # cfg (hence every plan, workspace and captured graph made from it) was fixed by the operator the block was built with
+            raise ValueError(f"STConvBlock was built with a {'sparse' if self.cfg.sparse_gso else 'dense'} gso and now holds a "
+                             f"{'sparse' if sparse else 'dense'} one: build the model with the operator kind it is to run with")
+        if sparse:
+            # a sparse tensor has no data_ptr(): the cache is keyed on its index and value arrays (a sparse operator selects the CSR graph conv)
+            parts = (gso.crow_indices(), gso.col_indices(), gso.values()) if gso.layout == torch.sparse_csr else (gso._indices(), gso._values())
+            key = ("sparse", str(gso.layout), tuple(gso.shape)) + tuple((t.data_ptr(), t._version, t.numel()) for t in parts) + (str(device),)
+        else:
+            key = (gso.data_ptr(), gso._version, str(device), ops.gc_layout_epoch())
         if self._gso_cache is None or self._gso_cache[0] != key:
             gp, gt = ops.gso_prepare(gso.to(device), ops.graph_terms(self.cfg))
             self._gso_cache = (key, gp, gt)

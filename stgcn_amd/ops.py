@@ -33,6 +33,7 @@ class BlockConfig:
     droprate: float
     ln_eps: float = 1e-12
     tag: int = 0          # block index: labels the library's kernel timer only
+    sparse_gso: bool = False      # the operator is a pair of ``SparseGso`` (CSR blobs): STGCN_GC_CHEB_CSR / STGCN_GC_KIPF_CSR
 
 
 def _stream_of(t: torch.Tensor) -> Optional[int]:
@@ -122,7 +123,7 @@ def make_desc(cfg: BlockConfig, B: int, T: int, training: bool, need_dx: bool, p
     d.c0, d.c1, d.c2 = cfg.channels
     d.Kt, d.Ks = cfg.Kt, cfg.Ks
     d.act = _lib.ACT[cfg.act_func]
-    d.graph_conv = _lib.GRAPH_CONV[cfg.graph_conv_type]
+    d.graph_conv = (_lib.GRAPH_CONV_CSR if cfg.sparse_gso else _lib.GRAPH_CONV)[cfg.graph_conv_type]
     d.training = 1 if training else 0
     d.droprate = float(cfg.droprate)
     d.ln_eps = float(cfg.ln_eps)
@@ -150,12 +151,108 @@ def query_plan(desc: StblockDesc) -> StblockPlan:
     return p
 
 
-def gso_prepare(gso: torch.Tensor, terms: int) -> Tuple[torch.Tensor, torch.Tensor]:
+SPARSE_LAYOUTS = (torch.sparse_csr, torch.sparse_coo)
+
+
+def is_sparse_gso(gso) -> bool:
+    """A graph shift operator that selects the sparse graph conv: a ``torch.sparse_csr`` / ``sparse_coo`` tensor."""
+    return torch.is_tensor(gso) and gso.layout in SPARSE_LAYOUTS
+
+
+def _csr_release(dll, blob: torch.Tensor) -> None:
+    dll.stgcn_gso_csr_release(blob.data_ptr())      # (the blob is an argument of the finalizer: its memory outlives the registry entry)
+
+
+class SparseGso:
+    """One CSR operator as the sparse graph conv reads it (``stgcn_gso_csr_prepare``): the blob, registered with the library under its
+    address until this object is collected.  ``data_ptr()`` is what the block calls take in place of a dense operator's; ``decode()``
+    gives the arrays back (tests)."""
+
+    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int):
+        import weakref
+        L = _lib.lib()
+        _check_device(val, "sparse gso values")
+        assert rowptr.dtype == torch.int32 and col.dtype == torch.int32 and rowptr.device == col.device == val.device
+        assert rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()
+        self.N, self.nnz = int(N), int(col.numel())
+        words = C.c_int64(0)
+        L.check(L.dll.stgcn_gso_csr_layout(self.N, self.nnz, C.byref(words)), "stgcn_gso_csr_layout")
+        self.blob = torch.empty(int(words.value), dtype=torch.float32, device=val.device)
+        L.check(L.dll.stgcn_gso_csr_prepare(rowptr.data_ptr(), _optr(col) if self.nnz else None, _optr(val) if self.nnz else None, self.N, self.nnz,
+                                            self.blob.data_ptr(), _stream_of(val)), "stgcn_gso_csr_prepare")
+        if val.is_cuda:
+            torch.cuda.current_stream(val.device).synchronize()      # the arrays handed over are freed on return
+        self._finalizer = weakref.finalize(self, _csr_release, L.dll, self.blob)
+
+    def data_ptr(self) -> int:
+        return self.blob.data_ptr()
+
+    @property
+    def device(self):
+        return self.blob.device
+
+    def decode(self):
+        """(rowptr, col, val) as numpy arrays, read back from the blob."""
+        w = self.blob.cpu().numpy()
+        wi = w.view("int32")
+        assert wi[1] == self.N and wi[2] == self.nnz
+        up4 = lambda v: (v + 3) // 4 * 4
+        oc = 16 + up4(self.N + 1)
+        ov = oc + up4(self.nnz)
+        return wi[16:16 + self.N + 1].copy(), wi[oc:oc + self.nnz].copy(), w[ov:ov + self.nnz].copy()
+
+
+def _sparse_gso_prepare(gso: torch.Tensor) -> Tuple[SparseGso, SparseGso]:
+    """``gso_prepare`` for a ``sparse_csr`` / ``sparse_coo`` operator.  The index arrays are checked ONCE, here on the host, before anything
+    reaches the device (one synchronisation per model): lengths, a monotone row pointer, every index inside [0, N) -- ``ValueError``
+    otherwise.  Duplicates are summed and the columns of each row sorted with a stable sort of (row, col) keys; L^T comes from the same
+    entries sorted by (col, row), so both orders are functions of the input alone."""
+    if gso.dim() != 2 or gso.shape[0] != gso.shape[1]:
+        raise ValueError(f"sparse gso: a square matrix expected, got {tuple(gso.shape)}")
+    N, dev = int(gso.shape[0]), gso.device
+    if gso.layout == torch.sparse_csr:
+        crow, col, val = gso.crow_indices().detach().cpu().to(torch.int64), gso.col_indices().detach().cpu().to(torch.int64), gso.values().detach().cpu()
+        if crow.dim() != 1 or crow.numel() != N + 1 or col.dim() != 1 or val.dim() != 1 or col.numel() != val.numel():
+            raise ValueError(f"sparse gso: crow_indices of {N + 1} and col_indices / values of equal length expected, got {crow.numel()}, "
+                             f"{col.numel()}, {val.numel()}")
+        if int(crow[0]) != 0 or int(crow[-1]) != col.numel() or bool((crow[1:] < crow[:-1]).any()):
+            raise ValueError("sparse gso: crow_indices must rise monotonically from 0 to nnz")
+        row = torch.repeat_interleave(torch.arange(N, dtype=torch.int64), crow[1:] - crow[:-1])
+    else:
+        idx, val = gso._indices().detach().cpu().to(torch.int64), gso._values().detach().cpu()
+        if idx.dim() != 2 or idx.shape[0] != 2 or val.dim() != 1 or idx.shape[1] != val.numel():
+            raise ValueError(f"sparse gso: indices of shape (2, nnz) and nnz scalar values expected, got {tuple(idx.shape)}, {tuple(val.shape)}")
+        row, col = idx[0], idx[1]
+        if row.numel() and (int(row.min()) < 0 or int(row.max()) >= N):
+            raise ValueError(f"sparse gso: row index outside [0, {N})")
+    if col.numel() and (int(col.min()) < 0 or int(col.max()) >= N):
+        raise ValueError(f"sparse gso: column index outside [0, {N})")
+    val = val.to(torch.float32)
+    # coalesce: stable sort by (row, col), duplicates summed in stored order (CPU index_add_: sequential)
+    key = row * N + col
+    order = torch.sort(key, stable=True).indices
+    ukey, inv = torch.unique_consecutive(key[order], return_inverse=True)
+    uval = torch.zeros(ukey.numel(), dtype=torch.float32).index_add_(0, inv, val[order])
+    urow, ucol = torch.div(ukey, N, rounding_mode="floor"), ukey % N
+
+    def csr(r, c, v):
+        o = torch.sort(r * N + c, stable=True).indices
+        ptr = torch.zeros(N + 1, dtype=torch.int64)
+        ptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), 0)
+        return SparseGso(ptr.to(torch.int32).to(dev), c[o].to(torch.int32).contiguous().to(dev), v[o].contiguous().to(dev), N)
+    return csr(urow, ucol, uval), csr(ucol, urow, uval)
+
+
+def gso_prepare(gso: torch.Tensor, terms: int):
     """Once per model (main.py:101-103 upload): the dense (N, N) graph shift operator in the layout the graph-conv kernels
     read (``stgcn_gso_layout``).  Up to 512 nodes: the Chebyshev polynomials T_1 .. T_{terms-1} and their transposes, zero
     padded and in MFMA fragment order; beyond (tiled graph conv): the dense zero-padded operator and its transpose.
     ``terms`` = operator terms of the graph conv including the identity: Ks for ChebGraphConv, 2 for GraphConv
-    (``graph_terms``)."""
+    (``graph_terms``).
+    A ``torch.sparse_csr`` / ``sparse_coo`` operator gives a pair of ``SparseGso`` (L, L^T) instead, for blocks whose ``BlockConfig`` has
+    ``sparse_gso=True``: the recursion then runs on the activations for any node count, work and memory follow nnz."""
+    if gso.layout in SPARSE_LAYOUTS:
+        return _sparse_gso_prepare(gso.detach())
     L = _lib.lib()
     gso = gso.detach().to(torch.float32).contiguous()
     _check_device(gso, "gso")
@@ -759,7 +856,9 @@ class _STBlockFn(torch.autograd.Function):
             if hk.rowstat:      # (NULL: the library forms no row partials in consumers -- STGCN_FUSE without bit 4 -- so nothing is offered)
                 ctx.own_hook = LnHookState(hk, (ws, ps, offset_dev))      # (y itself is pinned by the _ln_hooks entry)
                 _offer_ln_hook(y, ctx.own_hook)
-        ctx.save_for_backward(x_cl, saved, gso_t_pad, y, *[p for p in params if p is not None])
+        # (a SparseGso is no tensor: its blob is saved, and the object itself keeps the blob registered until the backward ran)
+        ctx.gso_t_keep = gso_t_pad
+        ctx.save_for_backward(x_cl, saved, gso_t_pad if torch.is_tensor(gso_t_pad) else gso_t_pad.blob, y, *[p for p in params if p is not None])
         ctx.param_present = [p is not None for p in params]
         ctx.cfg, ctx.training, ctx.seed, ctx.offset, ctx.wsc, ctx.ws = cfg, training, seed, offset, wsc, ws
         ctx.offset_dev = offset_dev

@@ -121,6 +121,32 @@ def run_collective_capture_child(env: dict, timeout_s: float = 60.0) -> Tuple[bo
     return ok, why
 
 
+def _broadcast_sparse_operator(gso: torch.Tensor, comm_dev, src: int) -> torch.Tensor:
+    """Rank ``src``'s sparse operator on every rank: the ranks may hold different numbers of stored entries, so the lengths go first, then
+    the index and value arrays (a sparse tensor itself cannot be broadcast).  Returns a ``sparse_csr`` / ``sparse_coo`` tensor on ``comm_dev``."""
+    csr = gso.layout == torch.sparse_csr
+    if not csr and gso.layout != torch.sparse_coo:
+        raise ValueError(f"sync_operators: a strided, sparse_csr or sparse_coo operator expected, got {gso.layout}")
+    # int64 indices and float32 values on every rank, whatever each rank built its own operator with: the receive buffers must match the sender's
+    mine = (gso.crow_indices(), gso.col_indices(), gso.values()) if csr else (gso._indices(), gso._values())
+    mine = tuple(t.detach().to(torch.int64) for t in mine[:-1]) + (mine[-1].detach().to(torch.float32),)
+    meta = torch.tensor([1 if csr else 0, gso.shape[0], gso.shape[1]] + [t.numel() for t in mine] + [0] * (3 - len(mine)), dtype=torch.int64,
+                        device=comm_dev)
+    dist.broadcast(meta, src=src)
+    src_csr, rows, cols, *lens = (int(v) for v in meta.tolist())
+    if bool(src_csr) != csr:
+        raise ValueError("sync_operators: the ranks hold sparse operators of different layouts")
+    out = []
+    for i, t in enumerate(mine):
+        shape = (2, lens[i] // 2) if (not csr and i == 0) else (lens[i],)
+        b = t.detach().to(comm_dev, copy=True).contiguous() if dist.get_rank() == src else torch.empty(shape, dtype=t.dtype, device=comm_dev)
+        dist.broadcast(b, src=src)
+        out.append(b)
+    if csr:
+        return torch.sparse_csr_tensor(out[0], out[1], out[2], size=(rows, cols))
+    return torch.sparse_coo_tensor(out[0], out[1], size=(rows, cols))
+
+
 def sync_operators(model, src: int = 0) -> None:
     """Data-parallel replicas must train with ONE graph shift operator: ``gso`` is a plain attribute (not a parameter, not a
     buffer, never all-reduced -- layers.py:128/179 of the reference), and the reference's ``calc_chebynet_gso`` depends on numpy's
@@ -138,9 +164,12 @@ def sync_operators(model, src: int = 0) -> None:
                 # that .to(device) never moved, so it is often still a CPU tensor) and the result goes back where the operator lived
                 home = m.gso.device
                 comm_dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-                t = m.gso.detach().to(comm_dev, copy=True).contiguous()
-                dist.broadcast(t, src=src)
-                g = t.to(home)
+                if m.gso.layout != torch.strided:
+                    g = _broadcast_sparse_operator(m.gso, comm_dev, src).to(home)
+                else:
+                    t = m.gso.detach().to(comm_dev, copy=True).contiguous()
+                    dist.broadcast(t, src=src)
+                    g = t.to(home)
                 seen[id(m.gso)] = g
             m.gso = g
             m.graph_conv.gso = g
