@@ -521,13 +521,34 @@ __device__ __forceinline__ int xcd_item(int b, int n) {
 __device__ __forceinline__ int pow2_shift(int d) { return (d > 0 && (d & (d - 1)) == 0) ? 31 - __builtin_clz((unsigned)d) : -1; }
 __device__ __forceinline__ int fast_div(int x, int d, int sh) { return sh >= 0 ? (x >> sh) : x / d; }
 
+// ReLU that hands a NaN on, as the reference's does (fmaxf(NaN, 0) is 0: a diverged activation would come out of the block finite and a
+// trainer's non-finite check would never see it).  DESIGN.md section 5, tests/conditioning_util.py.
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+
 // v_exp_f32 + v_rcp_f32 (1 ulp each), 4 instructions.  (__frcp_rn / "1.0f / x" expand to the 11-instruction IEEE divide
 // sequence, __expf to a range-reduced polynomial: together they were a quarter of the gated conv's row pass.)
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 
-// tanh(x) = 2 sigmoid(2x) - 1 on the same two hardware instructions (abs. error ~4e-7): libm's tanhf is a branchy ~60-instruction
-// call that the gated kernels would pay per element in forward AND backward (and that spilled the role-specialised kernels)
-__device__ __forceinline__ float tanh_f(float x) { return 2.0f * sigmoid_f(2.0f * x) - 1.0f; }
+// tanh on the same two hardware instructions, RELATIVE error <= 4 * 2^-24 on every input (libm's tanhf is a branchy ~60-instruction call
+// that the gated kernels would pay per element in forward AND backward, and that spilled the role-specialised kernels):
+//   |x| >= 0.625: 1 - 2 / (1 + E), E = exp(2 |x|): the quotient is at most 0.445 there, so its error enters a result of at least 0.555;
+//   |x| <  0.625: x + x^3 q(x^2), q of degree 4 (Chebyshev fit of (tanh(x) / x - 1) / x^2 on [0, 0.625^2], error 3e-9): any form that
+//                 subtracts from 1 keeps an ABSOLUTE error of 2^-24 there -- a relative error 1e-7 / |x| of a value the LayerNorm behind
+//                 the gate rescales (the former 2 sigmoid(2x) - 1: 1e-3 of the stage at |u| ~ 2^-14).
+// Both are evaluated and one is selected (v_cndmask, no branch); NaN takes the exp form and stays NaN, +-inf gives +-1 (E = inf).  Each
+// form lives in one register beside x (tc2_ln_fwd_kernel's six-tile bf16 instance sits at its 128-VGPR bound).
+// tests/test_emu_conditioning.py sweeps it against float64 over 2^-40 <= |x| <= 16.
+__device__ __forceinline__ float tanh_f(float x) {
+    const float z = x * x;
+    float q = __builtin_fmaf(z, -0.006104947999119759f, 0.021003641188144684f);
+    q = __builtin_fmaf(z, q, -0.05385249853134155f);
+    q = __builtin_fmaf(z, q, 0.13332782685756683f);
+    q = __builtin_fmaf(z, q, -0.333333283662796f);
+    const float small = __builtin_fmaf(x, q * z, x);
+    const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fabsf(x) * 2.8853900817779268f));
+    const float big = __builtin_copysignf(__builtin_fmaf(-2.0f, r, 1.0f), x);
+    return __builtin_fabsf(x) < 0.625f ? small : big;
+}
 
 // ---- gate math (reference model/layers.py:105 GLU, :109 GTU) --------------------------------
 // forward: h = act(u) * s ; act = identity (glu) or tanh (gtu)
@@ -539,6 +560,25 @@ __device__ __forceinline__ void gate_bwd(float dh, float u, float s, int act, fl
         dq = dh * u * s * (1.0f - s);
     } else {
         const float th = tanh_f(u);
+        du = dh * s * __builtin_fmaf(-th, th, 1.0f);   // (explicit: the function is inlined at several call sites that must round alike)
+        dq = dh * th * s * (1.0f - s);
+    }
+}
+
+// The former tanh, 2 sigmoid(2x) - 1 (ABSOLUTE error 2^-24), and the gate math on it, for the output head's backward ONLY (ln_rowstat4's
+// U / S form and the LayerNorm + gate backward staged into the head's transposed conv).  Those kernels take `act` at run time, and the
+// compiler shapes their GLU code by the cost of the GTU arm beside it: while that arm is four instructions it selects instead of branching
+// and packs / contracts the row sums s2 += gg * xh one way, with tanh_f there another -- the GLU gradients of the benchmarked head moved by
+// 1e-7 relative, and a training run by more than rounding after a few hundred steps.  The head's gate inputs are the conv of a block's
+// LayerNorm output, O(1), where an absolute 2^-24 is fp32 rounding; every ST block kernel is on tanh_f.
+__device__ __forceinline__ float tanh_abs_f(float x) { return 2.0f * sigmoid_f(2.0f * x) - 1.0f; }
+__device__ __forceinline__ float gate_fwd_abs(float u, float s, int act) { return (act == 0 ? u : tanh_abs_f(u)) * s; }
+__device__ __forceinline__ void gate_bwd_abs(float dh, float u, float s, int act, float& du, float& dq) {
+    if (act == 0) {
+        du = dh * s;
+        dq = dh * u * s * (1.0f - s);
+    } else {
+        const float th = tanh_abs_f(u);
         du = dh * s * __builtin_fmaf(-th, th, 1.0f);   // (explicit: the function is inlined at several call sites that must round alike)
         dq = dh * th * s * (1.0f - s);
     }
@@ -719,7 +759,8 @@ __device__ __forceinline__ float2 ld2_sc1(const float2* base, long nelem, int id
 }
 // ---- "bf16x6": fp32-accurate matrix products on the bf16 matrix pipe (round 6) -----------------------------------------------------------
 // An fp32 value splits EXACTLY into three bf16 numbers, x = h + m + l (8 + 8 + 8 significand bits; each residual is exact in fp32).  A product
-// of two such values is 9 terms; the three smallest (m l, l m, l l: below 2^-32 of the product) are dropped, the other six are formed EXACTLY
+// of two such values is 9 terms; the three smallest (m l and l m up to about 2^-27 of the product each, l l far below: about 2^-26 of
+// a product dropped) are dropped, the other six are formed EXACTLY
 // by bf16 multiplies and accumulated in fp32 by the matrix pipe: the same 2^-24-per-product accuracy class as v_mfma_f32_16x16x4_f32, at
 // 3 x 17.5 cycles per 16-deep step instead of 4 x 32 -- and a bf16 MFMA does not exclude the SIMD's VALU (profiles/r6-01_valu_mfma_overlap.txt).
 // Two terms share one 32-deep instruction: slots 0..3 / 4..7 of a lane's operand hold a lane's 4 k values of two PLANES,

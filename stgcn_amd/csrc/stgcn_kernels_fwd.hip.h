@@ -767,7 +767,7 @@ __device__ __forceinline__ float2 ln_rowstat4(const LnRowstatOut& o, uint64_t of
     for (int i = 0; i < 4; ++i) dy[i] *= k[i];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float xh = (gate_fwd(u[i], s[i], o.act) - mean) * rstd;
+        const float xh = (gate_fwd_abs(u[i], s[i], o.act) - mean) * rstd;   // (stgcn_device.hip.h: tanh_abs_f)
         const float gg = dy[i] * ga[i];
         s1 += gg;
         s2 += gg * xh;
@@ -914,11 +914,11 @@ __device__ __forceinline__ void tconv_fwd4_body(const Tconv4Args& aa, const Head
                     f32x4 du, dq, dg;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float xh = (gate_fwd(u[i], sg[i], b.act) - mean) * rstd;
+                        const float xh = (gate_fwd_abs(u[i], sg[i], b.act) - mean) * rstd;   // (stgcn_device.hip.h: tanh_abs_f)
                         const float dh = rstd * (dy[i] * ga[i] - c1 - xh * c2);
                         dg[i] = dy[i] * xh;
                         float du_, dq_;
-                        gate_bwd(dh, u[i], sg[i], b.act, du_, dq_);
+                        gate_bwd_abs(dh, u[i], sg[i], b.act, du_, dq_);
                         du[i] = du_;
                         dq[i] = dq_;
                     }
@@ -1193,7 +1193,7 @@ __device__ __forceinline__ void tconv_fwd4_body(const Tconv4Args& aa, const Head
                 const long R = row0 + row;
                 f32x4 h = ld4(Zt + row * LDZ + COUT + 4 * c4);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) h[i] = fmaxf(h[i] + b1[i], 0.f);
+                for (int i = 0; i < 4; ++i) h[i] = relu_f(h[i] + b1[i]);
                 if (f.training) {
                     const f32x4 k = dropout_scale4((uint64_t)R * C4N + c4, f.seed, off, f.thresh, f.keep_scale);
 #pragma unroll
@@ -1468,7 +1468,7 @@ __device__ __forceinline__ void gconv_fwd_body(const GconvFwdArgs& a, const int 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int h = ht * 16 + 4 * g + r;
-                    if (h < N) stx1(G_ + ((size_t)(slab0 + j) * N + h) * 16 + l15, fmaxf(yacc[q][j][r] + bb + res[q][j][r], 0.f));
+                    if (h < N) stx1(G_ + ((size_t)(slab0 + j) * N + h) * 16 + l15, relu_f(yacc[q][j][r] + bb + res[q][j][r]));
                 }
             }
         }

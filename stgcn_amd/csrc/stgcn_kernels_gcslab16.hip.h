@@ -206,7 +206,7 @@ __global__ __launch_bounds__(MAXW * 64) void gconv_fwd16_kernel(GconvFwdArgs a) 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int h = ht * 16 + 4 * g + r;
-                if (h < N) a.G[((size_t)slab * N + h) * 16 + l15] = fmaxf(yacc[q][r] + bb + res[q][r], 0.f);
+                if (h < N) a.G[((size_t)slab * N + h) * 16 + l15] = relu_f(yacc[q][r] + bb + res[q][r]);
             }
         }
     }

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void gconv_rows_fwd_kernel(GcRowsFwdArgs a) {
         if (in) {
             f32x4 v;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = fmaxf(o[i], 0.f);
+            for (int i = 0; i < 4; ++i) v[i] = relu_f(o[i]);
             stx4(G_ + (size_t)row * 16 + 4 * g, v);
         }
         wave_lds_sync();   // (the next tile overwrites it)

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void fc_fwd_kernel(FcFwdArgs a) {
             for (int i = 0; i < 4; ++i) h[i] += b1[i];
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = fmaxf(h[i], 0.f);
+        for (int i = 0; i < 4; ++i) h[i] = relu_f(h[i]);
         if (a.training) {
             const f32x4 k = dropout_scale4((uint64_t)R * c4n + c4, a.seed, off, a.thresh, a.keep_scale);
 #pragma unroll

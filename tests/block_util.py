@@ -116,7 +116,10 @@ class BlockOracle:
     computed once per ReLU side pattern (see backward)."""
 
     def __init__(self, c_in, channels, Kt, Ks, gct, act, N, B, T, gso=None, pdrop=0.5, param_seed=3, data_seed=11, oracle32=True, kink=True,
-                 ln_scale=None):
+                 ln_scale=None, kink_rel=False):
+        """kink_rel: the ReLU kink window is FWD_TOL of the LARGEST pre-activation instead of FWD_TOL itself (tests/conditioning_util.py: inputs
+        away from unit scale, where an absolute window holds every unit or none).  The default is the absolute window."""
+        self.kink_rel = bool(kink_rel)
         self.dtypes = (np.float64, np.float32) if oracle32 else (np.float64,)
         self.kink_on = kink      # False: the oracle keeps its own ReLU mask everywhere (the whole-tensor stage tests of tests/gpu_util.py)
         self.args = (c_in, tuple(channels), Kt, Ks, gct, act, N, B, T)
@@ -157,8 +160,15 @@ class BlockOracle:
         Wk = sv["Wk"]
         pre = sum(sv["Xs"][k] @ Wk[k] for k in range(Wk.shape[0])) + (0.0 if bp["gc_b"] is None else bp["gc_b"]) + sv["A"]
         assert np.array_equal(np.maximum(pre, 0.0) > 0, sv["G"] > 0)
-        self.kink = (np.abs(pre) < FWD_TOL) & bool(self.kink_on)
-        self.window_bar = 2.0 * pre.size * 2.0 * FWD_TOL / (float(pre.std()) * np.sqrt(2.0 * np.pi)) + 5.0
+        width, sigma = FWD_TOL, float(pre.std())
+        if self.kink_rel:
+            # rounding errors scale with the largest magnitude; the count is bounded through the density at zero of a normal distribution
+            # as before, with the scale of the BULK of the units (median |pre| / 0.6745, the same sigma on normal data) where one outlying
+            # node inflates the standard deviation
+            width = FWD_TOL * float(np.abs(pre).max())
+            sigma = min(sigma, float(np.median(np.abs(pre))) / 0.6745)
+        self.kink = (np.abs(pre) < width) & bool(self.kink_on)
+        self.window_bar = 2.0 * pre.size * 2.0 * width / (sigma * np.sqrt(2.0 * np.pi)) + 5.0
 
     def backward(self, G_lib, dy=None):
         """(dx64, g64, stages64, dx32, g32, kink metrics) with the units of the kink window on the side the library's saved G took.
@@ -219,7 +229,7 @@ def rowstats_launched(L, fn):
 
 def run_block_case(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso=None, seed=99, offset=3, pdrop=0.5, debug_stages=True,
                    oracle=None, oracle32=True, kink=True, outputs=None, consumer=None, consumer_shape=None, ln_scale=None, expect_rowstats=None,
-                   tamper=None, caches=None, data_seed=11, on_span=None):
+                   tamper=None, caches=None, data_seed=11, on_span=None, stages_out=None):
     """Returns the dict of errors described in the module docstring.  oracle: a BlockOracle of the same case to share between runs;
     outputs: a dict that receives y, dx and the parameter gradients (numpy) for bitwise comparisons between runs.
     consumer = "block" / "head" (consumer_shape: see make_consumer): the block's output goes straight into a second fused module Q, the
@@ -227,7 +237,9 @@ def run_block_case(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso
     out of Q's epilogue (or of the pass behind a Q kernel without one) and the block runs with dy_rowstats_ready.  expect_rowstats: the
     ln_bwd_rowstats launches that backward must contain.  ln_scale = (g, b): gamma = g * U(-1, 1), beta = b * U(-1, 1).
     tamper: see run_consumer.  caches: a dict that keeps the workspace caches of P and Q between calls (successive steps of one model);
-    data_seed: seed of x and of the external dy.  on_span(name, "begin" / "end"): see run_consumer."""
+    data_seed: seed of x and of the external dy.  on_span(name, "begin" / "end"): see run_consumer.
+    stages_out: a dict that receives the library's saved forward stages as arrays (U1, S1, A, X<k>, G, U2, S2, mean, rstd -- those the plan
+    stores), for metrics of the caller's own (tests/conditioning_util.py)."""
     L = bind(dev)
     cuda = str(dev).startswith("cuda")
     prev_debug = ops.set_debug_stages(bool(debug_stages))
@@ -283,8 +295,11 @@ def run_block_case(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso
         T1 = plan.T1
         terms = 2 if gct == "graph_conv" else Ks
 
-        def seg(buf, off, ref):
-            return float(np.abs(buf[off:off + ref.size].reshape(ref.shape) - ref).max())
+        def seg(buf, off, ref, name=None):
+            got = buf[off:off + ref.size].reshape(ref.shape)
+            if stages_out is not None and name is not None:
+                stages_out[name] = got
+            return float(np.abs(got - ref).max())
 
         err = {}
         # chained launches: the sticky error word (a bounded wait gave up) of both workspaces, and ticket / finished-workgroup words re-armed
@@ -292,17 +307,19 @@ def run_block_case(dev, c_in, channels, Kt, Ks, gct, act, N, B, T, training, gso
             cw = buf[plan.ws_chain:plan.ws_chain + 4].view(torch.int32).cpu().numpy()
             err[f"grad_none_ok.chain_words_{nm}"] = float(abs(cw[:3]).sum())
         if not plan.recompute_tc1:
-            err["fwd.U1"] = seg(svn, plan.sv_U1, sv["U1"])
-            err["fwd.S1"] = seg(svn, plan.sv_S1, sv["S1"])
-        err["fwd.A"] = seg(svn, plan.sv_A, sv["A"])
+            err["fwd.U1"] = seg(svn, plan.sv_U1, sv["U1"], "U1")
+            err["fwd.S1"] = seg(svn, plan.sv_S1, sv["S1"], "S1")
+        err["fwd.A"] = seg(svn, plan.sv_A, sv["A"], "A")
         for k in range(1, terms):
-            err[f"fwd.X{k}"] = seg(svn, plan.sv_Xk + (k - 1) * B * T1 * N * c1, sv["Xs"][k])
-        err["fwd.G"] = seg(svn, plan.sv_G, sv["G"])
+            err[f"fwd.X{k}"] = seg(svn, plan.sv_Xk + (k - 1) * B * T1 * N * c1, sv["Xs"][k], f"X{k}")
+        err["fwd.G"] = seg(svn, plan.sv_G, sv["G"], "G")
         if plan.stored_US2:
-            err["fwd.U2"] = seg(svn, plan.sv_U2, sv["U2"])
-            err["fwd.S2"] = seg(svn, plan.sv_S2, sv["S2"])
-        err["fwd.mean"] = seg(svn, plan.sv_mean, sv["mean"])
+            err["fwd.U2"] = seg(svn, plan.sv_U2, sv["U2"], "U2")
+            err["fwd.S2"] = seg(svn, plan.sv_S2, sv["S2"], "S2")
+        err["fwd.mean"] = seg(svn, plan.sv_mean, sv["mean"], "mean")
         err["fwd.rstd_rel"] = float(np.abs(svn[plan.sv_rstd:plan.sv_rstd + B * T2].reshape(B, T2) / sv["rstd"] - 1).max())
+        if stages_out is not None:
+            stages_out["rstd"] = svn[plan.sv_rstd:plan.sv_rstd + B * T2].reshape(B, T2)
         y_cl = cl(y.detach().cpu().numpy())
         err["fwd.y"] = float(np.abs(y_cl.astype(np.float64) - y_ref).max())
         err["fwd.y_repeat_bitwise"] = float((y2 != y.detach().permute(0, 2, 3, 1)).sum().item())

@@ -88,6 +88,28 @@ def _build(force, opt):
     return OUT
 
 
+def build_probe():
+    """tests/emu/scalar_probe.cpp -> _build/libscalar_probe.so: the scalar device functions (tanh_f, gate_bwd, relu_f) for the host, a
+    one-second compile of stgcn_device.hip.h alone.  Rebuilt when the header, the shim or the probe is newer."""
+    cxx = find_clang()
+    if cxx is None:
+        raise RuntimeError("host clang++ not found (needed for ext_vector_type)")
+    out = os.path.join(EMU, "_build", "libscalar_probe.so")
+    srcs = [os.path.join(EMU, "scalar_probe.cpp"), os.path.join(EMU, "hip", "hip_runtime.h"), os.path.join(CSRC, "stgcn_device.hip.h")]
+    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    tmp = out + ".tmp.%d" % os.getpid()
+    try:
+        subprocess.run([cxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-I", EMU, "-I", CSRC, "-Wno-unused-value", "-Wno-vla-cxx-extension",
+                        srcs[0], "-o", tmp], check=True)
+        os.replace(tmp, out)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return out
+
+
 if __name__ == "__main__":
     import sys
     print(build(force=True, asan="--asan" in sys.argv, race="--race" in sys.argv))

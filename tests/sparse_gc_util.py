@@ -97,15 +97,17 @@ def case_oracle(name):
     return _oracles[name]
 
 
-def run_case(dev, name, sparse=True, dtype=torch.float32, seed=99, offset=3):
+def run_case(dev, name, sparse=True, dtype=torch.float32, seed=99, offset=3, oracle=None):
     """One forward + backward of case `name` on `dev`: sparse=True through the CSR path, False through whatever path the DENSE operator
     takes under the current knobs.  Returns (O, out): the case's BlockOracle with its forward computed for this run's dropout mask, and a
     dict of float arrays -- A, X1.., G, y (channels-last), dA, dx (channels-last or None), grad.<param> -- read back from the library's
-    buffers (bf16 tensors converted)."""
+    buffers (bf16 tensors converted).  oracle: a BlockOracle of the case's shape and operator with inputs of the caller's own
+    (tests/conditioning_util.py); None: the shared case_oracle(name)."""
     L = bind(dev)
     cuda = str(dev).startswith("cuda")
     c_in, channels, Kt, Ks, gct, act, N, B, T, training, _ = CASES[name]
-    O = case_oracle(name)
+    O = case_oracle(name) if oracle is None else oracle
+    assert O.args == CASES[name][:9]
     bf = dtype == torch.bfloat16
     dense, sparse_t = case_operator(name)
     bcfg = ops.BlockConfig(Kt=Kt, Ks=Ks, n_vertex=N, c_in=c_in, channels=tuple(channels), act_func=act, graph_conv_type=gct, droprate=O.pdrop,
